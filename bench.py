@@ -16,7 +16,11 @@ into its Window.py sections (repeatresolver_amd/window.py), the sections are dea
 collective: a section is an independent MSA), a step realigns the next slab of every section, and the
 totals are reduced over RCCL.  Fixed total work => "scaling": "strong".
 
-    python bench.py --gpus 1 --steps K --warmup W
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, print the line.  --full adds
+what it does not need (the CPU baseline of oracle/ on a bounded sample, and the --deadline-s guard, default 500 s there);
+--dump-outputs DIR writes what the last timed step left the caller as DIR/<name>.npy (see dump_outputs).
+
+    python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 """
 import argparse
@@ -79,6 +83,45 @@ def cpu_baseline(rows, bandwidth, budget_s=15.0):
                       f"oracle/pw_oracle.c -O2, array-based restatement pinned to the reference by tests/golden)"}
 
 
+def dump_outputs(out_dir, ctxs, k0, k1, seed=0):
+    """What the timed path hands a caller after its last step, as .npy files (float32/float64, < 64 MB in all).  Per
+    context of this rank (prefix `unit<i>_` when there are several, in the order of `units`) the MSA as export_rows returns it:
+      total_score.npy      float64 (1,)      sum-of-pairs score of the whole MSA (OverallScorePrint)
+      msa_shape.npy        float64 (2,)      rows, columns
+      step_rows.npy        float64 (n,)      the rows [k0, k1) the last step realigned
+      step_row_bases.npy   float64 (n, 4)    per such row: bases, sum of their column ordinals, first and last base column (-1: none)
+      sample_rows.npy      float64 (s,)      a fixed, seeded sample of those rows ...
+      sample_msa.npy       float32 (s, W)    ... byte for byte (the character codes of the exported row)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    budget = 48e6 / max(1, len(ctxs))                        # bytes of sample_msa per context
+    for ci, g in enumerate(ctxs):
+        pre = f"unit{ci}_" if len(ctxs) > 1 else ""
+        exp = g.export_rows()
+        Tc, Wc = len(exp), (len(exp[0]) if exp else 0)
+        rows_k = np.arange(min(k0, Tc), min(k1, Tc))
+        per_row = np.full((len(rows_k), 4), -1.0)
+        cols = np.arange(Wc, dtype=np.float64)
+        for c0 in range(0, len(rows_k), 64):
+            a = np.frombuffer(b"".join(exp[k] for k in rows_k[c0:c0 + 64]), np.uint8).reshape(-1, Wc)
+            low = a | 0x20
+            base = (low >= ord("a")) & (low <= ord("z"))
+            n = base.sum(1)
+            per_row[c0:c0 + len(a), 0] = n
+            per_row[c0:c0 + len(a), 1] = base @ cols
+            per_row[c0:c0 + len(a), 2] = np.where(n > 0, base.argmax(1), -1)
+            per_row[c0:c0 + len(a), 3] = np.where(n > 0, Wc - 1 - base[:, ::-1].argmax(1), -1)
+        s = int(min(64, len(rows_k), budget // max(1, 4 * Wc)))
+        pick = np.sort(np.random.default_rng(seed).choice(rows_k, size=s, replace=False)) if s else rows_k[:0]
+        sample = np.frombuffer(b"".join(exp[k] for k in pick), np.uint8).reshape(s, Wc).astype(np.float32)
+        arrays = {"total_score": np.array([g.total_score()], dtype=np.float64), "msa_shape": np.array([Tc, Wc], dtype=np.float64),
+                  "step_rows": rows_k.astype(np.float64), "step_row_bases": per_row,
+                  "sample_rows": pick.astype(np.float64), "sample_msa": sample}
+        for name, arr in arrays.items():
+            np.save(os.path.join(out_dir, pre + name + ".npy"), arr)
+        del exp
+
+
 def opt_or_none(ctx, key):
     """an option's value, None for a library that does not know it (scripts/dev/ab.sh runs older builds)"""
     try:
@@ -118,12 +161,19 @@ def main():
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE", help="any other knob of pwr_set_option (include/pwr.h), e.g. seg_rows=512")
     ap.add_argument("--time-every", type=int, default=8, help="HIP events around every n-th fill launch (an event record costs ~6 us of stream time; 1 = every launch)")
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--deadline-s", type=float, default=500.0,
-                    help="N = 1: once the process has run this long, the line is printed for the steps finished so far (no further step is started)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--deadline-s", type=float, default=None,
+                    help="N = 1: once the process has run this long, the line is printed for the steps finished so far (no further step is started); "
+                         "default: none (500 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: the CPU baseline (oracle/, 15 s of CPU time) and the --deadline-s guard")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left the caller (the realigned MSA, reduced: see dump_outputs) as DIR/<name>.npy")
     ap.add_argument("--backend", default="nccl", help="process-group backend for --gpus > 1 (nccl = RCCL; gloo for rehearsals)")
     ap.add_argument("--one-device", action="store_true", help="rehearsal on a 1-GPU box: every rank uses device 0")
     args = ap.parse_args()
+    if args.deadline_s is None and args.full:
+        args.deadline_s = 500.0
 
     import torch
     import torch.distributed as dist
@@ -353,10 +403,10 @@ def main():
         if world == 1 and args.sections:
             out["per_section"] = [{"section": units[ci][0], "seconds_in_calls": round(ctx_seconds[ci], 3), "cells": g.stats()["cells_reference"],
                                    "stalls": g.stats()["stalls"], "batches": g.stats()["batches"]} for ci, g in enumerate(ctxs)]
-        if world == 1 and not args.no_cpu_baseline and final:
+        if world == 1 and args.full and not args.no_cpu_baseline and final:
             note("timing the CPU baseline on a bounded sample")
             out["cpu_baseline"] = cpu_baseline(rows, args.bandwidth)
-        elif world == 1 and not args.no_cpu_baseline:
+        elif world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = None
         print(json.dumps(out), flush=True)
 
@@ -374,11 +424,16 @@ def main():
         done = i + 1
         note(f"timed step {done}/{args.steps} done, {time.perf_counter() - t0:.1f} s")
         # A kill at the driver's limit must not leave the run without its line: past the deadline, report what is there.
-        if world == 1 and done < args.steps and time.time() - T_START > args.deadline_s:
+        if world == 1 and args.deadline_s is not None and done < args.steps and time.time() - T_START > args.deadline_s:
             note(f"deadline: reporting {done} finished steps")
             break
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        last = args.warmup + done - 1
+        k0, k1 = slab_bounds(T, args.slabs, last) if last >= 0 else (0, 0)
+        dump_outputs(args.dump_outputs, ctxs, k0, k1)
+        note(f"outputs of step {last} (rows [{k0}, {k1})) written to {args.dump_outputs}")
     report(done, dt, final=(done == args.steps))
     for g in ctxs:
         g.close()

@@ -462,3 +462,45 @@ def test_bench_two_ranks_rehearsal(split):
     assert ("sections" if split == "sections" else "replica") in d["config"]["workload"]
     if split == "rows":                                        # every replica committed every row of the two steps
         assert d["per_rank"][0]["cells"] == d["per_rank"][1]["cells"] == d["roofline"]["cells_reference"]
+
+
+def test_bench_one_gpu_plain_full_and_dumped_outputs(tmp_path):
+    """bench.py on one GPU as every pull request runs it: --steps is the number of timed steps; a plain run leaves the CPU
+    baseline out and --full puts it back; --dump-outputs writes, for the same arguments, the same arrays, and they are
+    the state the last timed step left (its rows, the score and shape the result line reports)."""
+    import subprocess
+    import sys
+    import numpy as np
+    from conftest import ROOT
+
+    def bench(*extra):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "tree_medium", *extra]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
+        assert p.returncode == 0, p.stderr[-2000:]
+        return json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+
+    runs = []
+    for name in ("a", "b"):
+        d = bench("--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / name))
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert (d["metric"], d["unit"], d["higher_is_better"], d["dtype"]) == ("sum-of-pairs DP cells/sec", "DP cells/s", True, "u32")
+        assert "cpu_baseline" not in d
+        runs.append(d)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) == sorted(
+        n + ".npy" for n in ("total_score", "msa_shape", "step_rows", "step_row_bases", "sample_rows", "sample_msa"))
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    out = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    for n in names:
+        assert out[n[:-4]].dtype in (np.float32, np.float64), n
+        assert np.array_equal(out[n[:-4]], np.load(tmp_path / "b" / n)), n
+    c = runs[0]["config"]
+    T = c["rows"]
+    assert out["total_score"].tolist() == [c["score_after"]] and out["msa_shape"].tolist() == [T, c["columns_now"]]
+    assert out["step_rows"].tolist() == list(range(3 * T // 8, 4 * T // 8))            # step 1 + 3 - 1 = slab 3 of round 0
+    assert out["sample_msa"].shape == (len(out["sample_rows"]), c["columns_now"]) and len(out["sample_rows"]) > 0
+    assert set(np.unique(out["sample_msa"]).astype(np.uint8).tobytes()) <= set(b"acgtACGT-_ ")
+    assert (out["step_row_bases"][:, 0] > 0).any()
+
+    d = bench("--steps", "1", "--warmup", "0", "--full")
+    assert d["steps"] == 1 and d["cpu_baseline"]["value"] > 0
