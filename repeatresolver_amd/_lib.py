@@ -29,6 +29,11 @@ EXPORTS = ["pwr_create", "pwr_destroy", "pwr_trim_ends", "pwr_realign_row", "pwr
 PIA_EXPORTS = ["pia_create", "pia_destroy", "pia_align", "pia_get_stats", "pia_set_option", "pia_get_timing", "pia_read_template", "pia_read_fasta",
                "pia_build_msa", "pia_run_files"]
 
+# every symbol include/prc.h declares (the ReadCutter, the pipeline's first tool)
+PRC_EXPORTS = ["prc_create", "prc_destroy", "prc_occurrences", "prc_cut", "prc_get_stats", "prc_free", "prc_read_template",
+               "prc_read_fasta", "prc_scan_dense", "prc_scan_runs", "prc_select_cuts", "prc_write_seq", "prc_write_info",
+               "prc_run_files"]
+
 # every symbol include/pmc.h declares (MaxCorrelation)
 PMC_EXPORTS = ["pmc_maxcorrs", "pmc_last_timing", "pmc_read_msa", "pmc_write", "pmc_run_file"]
 
@@ -132,5 +137,34 @@ def load():
     lib.pmc_read_msa.argtypes = [ctypes.c_char_p, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_void_p)]
     lib.pmc_write.restype = ci
     lib.pmc_write.argtypes = [ctypes.c_char_p, ci, ctypes.POINTER(ctypes.c_double)]
+    pi, pll, cp = ctypes.POINTER(ci), ctypes.POINTER(ll), ctypes.c_char_p
+    lib.prc_create.restype = ci
+    lib.prc_create.argtypes = [ctypes.POINTER(vp), cp, ci, ci]
+    lib.prc_destroy.restype = None
+    lib.prc_destroy.argtypes = [vp]
+    lib.prc_occurrences.restype = ci
+    lib.prc_occurrences.argtypes = [vp, ci, cp, pll, ci, ci, ctypes.c_double, pll, ctypes.POINTER(vp)]
+    lib.prc_cut.restype = ci
+    lib.prc_cut.argtypes = [vp, ci, cp, pll, ci, ci, ctypes.c_double, pi, ctypes.POINTER(vp)]
+    lib.prc_get_stats.restype = ci
+    lib.prc_get_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double)]
+    lib.prc_free.restype = None
+    lib.prc_free.argtypes = [vp]
+    lib.prc_read_template.restype = ci
+    lib.prc_read_template.argtypes = [cp, ctypes.POINTER(vp), pi]
+    lib.prc_read_fasta.restype = ci
+    lib.prc_read_fasta.argtypes = [cp, pi, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), pi]
+    lib.prc_scan_dense.restype = ci
+    lib.prc_scan_dense.argtypes = [pi, ci, ci, ci, pi]
+    lib.prc_scan_runs.restype = ci
+    lib.prc_scan_runs.argtypes = [pi, ci, ci, pi]
+    lib.prc_select_cuts.restype = ci
+    lib.prc_select_cuts.argtypes = [ci, ci, ci, ci, pi, ci, pi, ci, pi]
+    lib.prc_write_seq.restype = ci
+    lib.prc_write_seq.argtypes = [cp, ci, cp, pll, pi, pi]
+    lib.prc_write_info.restype = ci
+    lib.prc_write_info.argtypes = [cp, ci, pi]
+    lib.prc_run_files.restype = ci
+    lib.prc_run_files.argtypes = [cp, cp, cp, cp, ci, ci, ctypes.c_double, ci, ci, vp]
     _lib = lib
     return lib

@@ -40,3 +40,50 @@ def initial_msa(cfg: dg.SimConfig, device: int = 0, cutoff: float = 0.30):
             "rejected_by_cutoff": classes.count("l"), "cells": st["cells"], "align_ms": st["last_align_ms"],
             "simulate_s": round(t1 - t0, 1), "align_s": round(t2 - t1, 2), "build_msa_s": round(time.time() - t2, 1)}
     return rows, info
+
+
+def initial_msa_from_reads(cfg: dg.SimConfig, device: int = 0, cutoff: float = 0.30, parts: int = 60, overlap: int = 0,
+                           error_cutoff: float = 0.30):
+    """The reference pipeline's own way in, from the *full* reads (no ground truth): writes the data set's reads FASTA
+    (datagen.write_dataset), runs the ReadCutter drop-in on it (GPU), then InitialAligner (GPU) on the Seq.fasta it wrote.
+    Returns (rows, info) like initial_msa."""
+    from .initial_aligner import _clean
+    from .read_cutter import run_files
+    t0 = time.time()
+    tmp = tempfile.mkdtemp(prefix="prc_msa_")
+    try:
+        dg.write_dataset(os.path.join(tmp, "ds"), cfg)
+        templ_path = os.path.join(tmp, "dsTemplate.fasta")
+        os.replace(os.path.join(tmp, "ds_Template.fasta"), templ_path)
+        seq_path, rsi_path = os.path.join(tmp, "cut_Seq.fasta"), os.path.join(tmp, "cut_ReadSeqInfo")
+        t1 = time.time()
+        code, out = run_files(templ_path, os.path.join(tmp, "ds.fasta"), seq_path, rsi_path, parts=parts, overlap=overlap,
+                              error_cutoff=error_cutoff, device=device)
+        if code != 0:
+            raise RuntimeError(f"ReadCutter failed ({code}): {out[-500:]}")
+        t2 = time.time()
+        with open(templ_path, "rb") as f:
+            templ = _clean(b"".join(ln for ln in f.read().split(b"\n") if not ln.startswith(b">")))
+        with open(seq_path, "rb") as f:
+            reads = [_clean(r) for r in f.read().split(b">")[1:]]
+        g = InitialAligner(templ, device=device)
+        try:
+            place, dist = g.align(reads)
+            st = g.stats()
+            t3 = time.time()
+            msa_path, cls_path = os.path.join(tmp, "MSA"), os.path.join(tmp, "SeqClass")
+            g.build_msa(msa_path, cls_path, reads, place, dist, cutoff)
+        finally:
+            g.close()
+        with open(msa_path, "rb") as f:
+            rows = f.read().split(b"\n")
+        with open(cls_path) as f:
+            classes = f.read().split()
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    if rows and rows[-1] == b"":
+        rows.pop()
+    info = {"pieces": len(reads), "bases": sum(len(r) for r in reads), "template": len(templ), "rows": len(rows),
+            "rejected_by_cutoff": classes.count("l"), "cells": st["cells"], "write_dataset_s": round(t1 - t0, 1),
+            "read_cutter_s": round(t2 - t1, 2), "align_s": round(t3 - t2, 2), "build_msa_s": round(time.time() - t3, 1)}
+    return rows, info
