@@ -37,6 +37,27 @@ PRC_EXPORTS = ["prc_create", "prc_destroy", "prc_occurrences", "prc_cut", "prc_g
 # every symbol include/pmc.h declares (MaxCorrelation)
 PMC_EXPORTS = ["pmc_maxcorrs", "pmc_last_timing", "pmc_read_msa", "pmc_write", "pmc_run_file"]
 
+# every symbol include/pgr.h declares (RepeatResolver's group refinement)
+PGR_EXPORTS = ["pgr_refine", "pgr_free", "pgr_last_timing", "pgr_read_window", "pgr_window_free", "pgr_slice_maxcorrs",
+               "pgr_read_maxcorrs_file", "pgr_default_cutoff", "pgr_restrict_coverage"]
+
+
+class PgrWindow(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_int), ("kept_rows", ctypes.c_int), ("von", ctypes.c_int), ("bis", ctypes.c_int),
+                ("width", ctypes.c_int), ("sc", ctypes.c_int), ("kept", ctypes.POINTER(ctypes.c_ubyte)),
+                ("groups", ctypes.POINTER(ctypes.c_uint64)), ("local_coverage", ctypes.POINTER(ctypes.c_uint64)),
+                ("coverage", ctypes.POINTER(ctypes.c_int))]
+
+
+class PgrResult(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_int), ("kept_rows", ctypes.c_int), ("width", ctypes.c_int), ("sc", ctypes.c_int),
+                ("nsig", ctypes.c_int), ("cutoff", ctypes.c_double), ("kept", ctypes.POINTER(ctypes.c_ubyte)),
+                ("maxcorrs", ctypes.POINTER(ctypes.c_double)), ("significant", ctypes.POINTER(ctypes.c_int)),
+                ("sizes", ctypes.POINTER(ctypes.c_int)), ("cliques", ctypes.POINTER(ctypes.c_int)),
+                ("cutoffs", ctypes.POINTER(ctypes.c_int)), ("drop_off", ctypes.POINTER(ctypes.c_double)),
+                ("c_groups", ctypes.POINTER(ctypes.c_uint64)), ("c_coverage", ctypes.POINTER(ctypes.c_uint64))]
+
+
 _lib = None
 
 
@@ -166,5 +187,24 @@ def load():
     lib.prc_write_info.argtypes = [cp, ci, pi]
     lib.prc_run_files.restype = ci
     lib.prc_run_files.argtypes = [cp, cp, cp, cp, ci, ci, ctypes.c_double, ci, ci, vp]
+    pd = ctypes.POINTER(ctypes.c_double)
+    lib.pgr_refine.restype = ci
+    lib.pgr_refine.argtypes = [ci, ci, cp, pd, ci, ci, ci, ctypes.c_double, ci, ctypes.POINTER(PgrResult)]
+    lib.pgr_free.restype = None
+    lib.pgr_free.argtypes = [ctypes.POINTER(PgrResult)]
+    lib.pgr_last_timing.restype = ci
+    lib.pgr_last_timing.argtypes = [pd]
+    lib.pgr_read_window.restype = ci
+    lib.pgr_read_window.argtypes = [ci, ci, cp, ci, ci, ctypes.POINTER(PgrWindow)]
+    lib.pgr_window_free.restype = None
+    lib.pgr_window_free.argtypes = [ctypes.POINTER(PgrWindow)]
+    lib.pgr_slice_maxcorrs.restype = ci
+    lib.pgr_slice_maxcorrs.argtypes = [pd, ci, ci, ci, pd]
+    lib.pgr_read_maxcorrs_file.restype = ci
+    lib.pgr_read_maxcorrs_file.argtypes = [cp, ci, ci, ctypes.POINTER(vp), pi]
+    lib.pgr_default_cutoff.restype = ctypes.c_double
+    lib.pgr_default_cutoff.argtypes = [ctypes.c_double, ci]
+    lib.pgr_restrict_coverage.restype = ci
+    lib.pgr_restrict_coverage.argtypes = [ci, pi, pd, pi]
     _lib = lib
     return lib

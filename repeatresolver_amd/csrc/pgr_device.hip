@@ -1,0 +1,365 @@
+// pgr_device.hip -- MI355X (gfx950) implementation of RepeatResolver's group refinement behind include/pgr.h.
+//
+// Reference: PhilippBongartz/RepeatResolver, RepeatResolver.c ("RR:"), Group_Refinement (RR:1634-1690): for every variation a
+// whose MaxCorrs exceed the cutoff, Cliquer (RR:1179-1240) scans every variation i of the window, scores the pair with four
+// sizes of intersections of row bit sets and one upper tail of a hypergeometric distribution (RR:472-488) and keeps the 29
+// best; the clique's row sets are then voted into a refined group and its coverage (RR:1460-1522, RR:976-1008, RR:1064-1096).
+//   k_gr_cliques  a tiled bit-set product like k_mc_pairs: a tile of PGR_TA significant a stays in LDS (their group and their
+//                 column's coverage, a chunk of words at a time), every thread owns one variation i per chunk of PGR_NT and
+//                 streams its two bit sets once.  A block walks a slice of the chunks and keeps, per a, the best 29 of its
+//                 slice in LDS; the running 29th value is the floor of the tail's early-out.
+//   k_gr_votes    one work-group per significant a: merges the slices' lists into the clique, then Sizes, the vote
+//                 histogram, Dropoff_Cutoff, and the refined group / coverage, one wave ballot per 64-row word.
+// TheBestUpdater (RR:1156-1176) never displaces on equality and inserts behind equal values, and the scan ascends in i: the
+// clique is the top 29 by (Z descending, i ascending), whatever the order of evaluation.  `better` below is that key.
+// This file is compiled with -ffp-contract=off: the saturated value 97.90 + F must be one division and one addition, so
+// that equal fractions give equal doubles here and on any host.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "hyper_tail.h"
+#include "pgr.h"
+
+#define PGR_TA 16                   // significant variations a per tile
+#define PGR_NT 256                  // threads per block = variations i per chunk
+#define PGR_WC 32                   // words per LDS chunk
+#define PGR_KEEP (PGR_MAXCLIQUE - 1) // partners kept per a
+#define PGR_MAXSLICES 16            // slices of the i range (partial lists per a)
+
+static double g_ms[5] = {0, 0, 0, 0, 0};
+
+// (z1, i1) ranks before (z2, i2)
+__device__ __forceinline__ bool better(double z1, int i1, double z2, int i2)
+{
+    return z1 > z2 || (z1 == z2 && i1 < i2);
+}
+
+// RR:472-488 Group_PositiveSignificance(G_i, G_a, LC_i, LC_a) from the four counts and the two group sizes.  `floor`: what a
+// value has to reach to matter (greedy, or the 29th of the running list).  The tail is at least its first term, so
+// -log10 pdf(schnitt) bounds the result from above; beyond 97.9 the value is 97.90 + F, which the first term does not bound.
+__device__ __noinline__ double d_gr_significance(const double *__restrict__ lnf, int schnitt, int cov, int gr1, int gr2, int size_i, int size_a, double floor)
+{
+    if (gr1 == 0 || gr2 == 0 || schnitt < 1) return 0.0;
+    if (schnitt <= gr2 && schnitt <= gr1 && gr1 - schnitt <= cov - gr2) {
+        const double zb = d_ln_hyper_pdf(lnf, (unsigned)schnitt, (unsigned)gr2, (unsigned)(cov - gr2), (unsigned)gr1) * -0.43429448190325182;
+        if (zb < floor - 1e-6 && zb < 97.9) return 0.0;
+    }
+    double Z = -1.0 * log10(d_hyper_Q(lnf, (unsigned)(schnitt - 1), (unsigned)gr2, (unsigned)(cov - gr2), (unsigned)gr1));   // RR:451-452
+    if (isinf(Z) || Z > 99) Z = 99.0;                                                                                       // RR:453
+    if (isinf(Z) || Z > 98.0) Z = 97.90 + (double)(2 * schnitt) / (double)(size_i + size_a);   // F_beta(., ., 1), RR:432-447: 2s + |i \ a| + |a \ i|
+    return Z;
+}
+
+// grid (tiles of a, slices of the i range); Svar = the significant variations, ascending; G[w][v], LC[w][column]
+__global__ __launch_bounds__(PGR_NT) void k_gr_cliques(int V, int W, int sc, int nS, const int *__restrict__ Svar,
+                                                       const unsigned long long *__restrict__ G, const unsigned long long *__restrict__ LC,
+                                                       const int *__restrict__ gsize, const double *__restrict__ lnf, int mincov4, double greedy,
+                                                       int cps, int nslices, double *__restrict__ pZ, int *__restrict__ pI)
+{
+    __shared__ unsigned long long sG[PGR_TA][PGR_WC], sL[PGR_TA][PGR_WC];
+    __shared__ double lZ[PGR_TA][32], cZ[PGR_NT];
+    __shared__ int lI[PGR_TA][32], lN[PGR_TA], cI[PGR_NT], s_cnt[PGR_TA], s_a[PGR_TA];
+    const int tid = threadIdx.x, a0 = blockIdx.x * PGR_TA, slice = blockIdx.y;
+    if (tid < PGR_TA) { s_a[tid] = a0 + tid < nS ? Svar[a0 + tid] : -1; lN[tid] = 0; }
+    const int nch = (V + PGR_NT - 1) / PGR_NT, ch0 = slice * cps, ch1 = min(nch, ch0 + cps);
+    for (int ch = ch0; ch < ch1; ++ch) {
+        const int i = ch * PGR_NT + tid;
+        const bool have = i < V;
+        const int ii = have ? i / 5 : 0;
+        int s[PGR_TA], g1[PGR_TA], g2[PGR_TA], cv[PGR_TA];
+#pragma unroll
+        for (int a = 0; a < PGR_TA; ++a) s[a] = g1[a] = g2[a] = cv[a] = 0;
+        for (int w0 = 0; w0 < sc; w0 += PGR_WC) {
+            __syncthreads();                                           // (everyone is done with the chunk before)
+            if (w0 == 0 && tid < PGR_TA) s_cnt[tid] = 0;
+            for (int t = tid; t < PGR_TA * PGR_WC; t += PGR_NT) {
+                const int a = t / PGR_WC, w = w0 + t % PGR_WC, va = s_a[a];
+                const bool ok = va >= 0 && w < sc;
+                sG[a][t % PGR_WC] = ok ? G[(size_t)w * V + va] : 0ull;
+                sL[a][t % PGR_WC] = ok ? LC[(size_t)w * W + va / 5] : 0ull;
+            }
+            __syncthreads();
+            if (have) {
+                const int wn = min(PGR_WC, sc - w0);
+                for (int w = 0; w < wn; ++w) {
+                    const unsigned long long gi = G[(size_t)(w0 + w) * V + i], li = LC[(size_t)(w0 + w) * W + ii];
+#pragma unroll
+                    for (int a = 0; a < PGR_TA; ++a) {
+                        const unsigned long long ga = sG[a][w], la = sL[a][w];
+                        s[a] += __popcll(gi & ga); g1[a] += __popcll(gi & la); g2[a] += __popcll(ga & li); cv[a] += __popcll(li & la);
+                    }
+                }
+            }
+        }
+        const int si = have ? gsize[i] : 0;
+#pragma unroll
+        for (int a = 0; a < PGR_TA; ++a) {
+            const int va = s_a[a];                                     // (the same for the whole block, as is every branch with a barrier)
+            if (va < 0) continue;
+            const int n = lN[a];
+            const double lastZ = n == PGR_KEEP ? lZ[a][PGR_KEEP - 1] : greedy;
+            const int lastI = n == PGR_KEEP ? lI[a][PGR_KEEP - 1] : -1;
+            double Z = 0.0;
+            if (have && i != va && s[a] > mincov4)                     // RR:1209, RR:1214
+                Z = d_gr_significance(lnf, s[a], cv[a], g1[a], g2[a], si, gsize[va], lastZ);
+            if (Z > greedy && (n < PGR_KEEP || better(Z, i, lastZ, lastI))) {      // RR:1217, RR:1158
+                const int slot = atomicAdd(&s_cnt[a], 1);              // (at most one per thread: slot < PGR_NT)
+                cZ[slot] = Z; cI[slot] = i;
+            }
+            __syncthreads();
+            const int cnt = s_cnt[a];
+            if (cnt == 0) continue;
+            // the new list = the best PGR_KEEP of list + candidates: everyone finds the rank of its entry among all of them
+            int rc = -1, rl = -1, myI = 0, eI = 0;
+            double myZ = 0.0, eZ = 0.0;
+            if (tid < cnt) {
+                myZ = cZ[tid]; myI = cI[tid]; rc = 0;
+                for (int t = 0; t < n; ++t) rc += better(lZ[a][t], lI[a][t], myZ, myI);
+                for (int t = 0; t < cnt; ++t) rc += better(cZ[t], cI[t], myZ, myI);
+            }
+            if (tid < n) {
+                eZ = lZ[a][tid]; eI = lI[a][tid]; rl = tid;
+                for (int t = 0; t < cnt; ++t) rl += better(cZ[t], cI[t], eZ, eI);
+            }
+            __syncthreads();
+            if (rc >= 0 && rc < PGR_KEEP) { lZ[a][rc] = myZ; lI[a][rc] = myI; }
+            if (rl >= 0 && rl < PGR_KEEP) { lZ[a][rl] = eZ; lI[a][rl] = eI; }
+            if (tid == 0) lN[a] = min(PGR_KEEP, n + cnt);
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+    for (int t = tid; t < PGR_TA * PGR_KEEP; t += PGR_NT) {
+        const int a = t / PGR_KEEP, k = t - a * PGR_KEEP;
+        if (s_a[a] < 0) continue;
+        const size_t o = ((size_t)(a0 + a) * nslices + slice) * PGR_KEEP + k;
+        const bool ok = k < lN[a];
+        pZ[o] = ok ? lZ[a][k] : 0.0;
+        pI[o] = ok ? lI[a][k] : -1;
+    }
+}
+
+// block = one significant variation
+__global__ __launch_bounds__(256) void k_gr_votes(int V, int W, int sc, int nk, int nslices, const int *__restrict__ Svar,
+                                                  const double *__restrict__ pZ, const int *__restrict__ pI,
+                                                  const unsigned long long *__restrict__ G, const unsigned long long *__restrict__ LC,
+                                                  int *__restrict__ cliques, int *__restrict__ sizes, int *__restrict__ cutoffs, double *__restrict__ drop_off,
+                                                  unsigned long long *__restrict__ cg, unsigned long long *__restrict__ cc)
+{
+    __shared__ double mZ[PGR_MAXSLICES * PGR_KEEP];
+    __shared__ int mI[PGR_MAXSLICES * PGR_KEEP], s_clique[PGR_MAXCLIQUE + 1], s_hist[32], s_sizes, s_nall, s_cut;
+    const int sidx = blockIdx.x, tid = threadIdx.x, a = Svar[sidx], tot = nslices * PGR_KEEP;
+    for (int t = tid; t < tot; t += 256) { mZ[t] = pZ[(size_t)sidx * tot + t]; mI[t] = pI[(size_t)sidx * tot + t]; }
+    if (tid <= PGR_MAXCLIQUE) s_clique[tid] = tid == 0 ? a : -1;      // RR:1196; unfilled slots and Clique[30] are -1 (RR:1229-1231)
+    if (tid < 32) s_hist[tid] = 0;
+    __syncthreads();
+    for (int t = tid; t < tot; t += 256) {
+        if (mI[t] < 0) continue;
+        int r = 0;
+        for (int u = 0; u < tot; ++u) r += mI[u] >= 0 && better(mZ[u], mI[u], mZ[t], mI[t]);
+        if (r < PGR_KEEP) s_clique[1 + r] = mI[t];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int n = 0, nall = 0;
+        while (s_clique[n] > 0) n++;                                   // RR:1650: variation 0 as a member ends the count
+        while (s_clique[nall] >= 0) nall++;                            // RR:982-989
+        s_sizes = n; s_nall = nall;
+        sizes[sidx] = n;
+    }
+    if (tid <= PGR_MAXCLIQUE) cliques[(size_t)sidx * (PGR_MAXCLIQUE + 1) + tid] = s_clique[tid];
+    __syncthreads();
+    const int n = s_sizes, nall = s_nall;
+    if (n <= 5) {                                                      // RR:1684-1687 (the host zeroes MaxCorrs[a])
+        if (tid == 0) { cutoffs[sidx] = 0; drop_off[sidx] = 1000.0; }
+        return;
+    }
+    const int wave = tid >> 6, lane = tid & 63;
+    for (int w = wave; w < sc; w += 4) {                               // RR:1471-1482: in how many of the first Sizes groups is the row
+        int v = 0;
+        for (int m = 0; m < n; ++m) v += (int)((G[(size_t)w * V + s_clique[m]] >> lane) & 1ull);
+        if (w * 64 + lane < nk && v > 0) atomicAdd(&s_hist[v], 1);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int sz[PGR_MAXCLIQUE + 2];                                     // sizes[k] = rows in more than k groups
+        int run = 0;
+        for (int k = PGR_MAXCLIQUE; k >= 0; --k) { run += k + 1 < 32 ? s_hist[k + 1] : 0; sz[k] = run; }
+        int c = 1;                                                     // RR:1487-1508
+        double min_drop = 1000000.0;
+        for (int k = 1; k < n - 1; ++k) {
+            const int m = min(nk - sz[k], sz[k]);
+            if (m > 0) {
+                const double drop = (double)(sz[k - 1] - sz[k + 1]) / (double)m;
+                if (drop < min_drop) { min_drop = drop; c = k; }
+            }
+        }
+        s_cut = c;
+        cutoffs[sidx] = c; drop_off[sidx] = min_drop;
+    }
+    __syncthreads();
+    const int c = s_cut;
+    for (int w = wave; w < sc; w += 4) {                               // RR:991-1006, RR:1079-1094: over ALL members
+        int vg = 0, vc = 0;
+        for (int m = 0; m < nall; ++m) {
+            const int mem = s_clique[m];
+            vg += (int)((G[(size_t)w * V + mem] >> lane) & 1ull);
+            vc += (int)((LC[(size_t)w * W + mem / 5] >> lane) & 1ull);
+        }
+        const bool in = w * 64 + lane < nk;
+        const unsigned long long bg = __ballot(in && vg > c), bc = __ballot(in && vc > c);
+        if (lane == 0) { cg[(size_t)sidx * sc + w] = bg; cc[(size_t)sidx * sc + w] = bc; }
+    }
+}
+
+#define HIPC(call)                                                                     \
+    do {                                                                               \
+        hipError_t e_ = (call);                                                        \
+        if (e_ != hipSuccess) {                                                        \
+            fprintf(stderr, "pgr: %s failed: %s\n", #call, hipGetErrorString(e_));    \
+            return PWR_ERR_DEVICE;                                                     \
+        }                                                                              \
+    } while (0)
+
+struct GrBufs {
+    unsigned long long *G = nullptr, *LC = nullptr, *cg = nullptr, *cc = nullptr;
+    int *gsize = nullptr, *Svar = nullptr, *pI = nullptr, *cliques = nullptr, *sizes = nullptr, *cutoffs = nullptr;
+    double *lnf = nullptr, *pZ = nullptr, *drop = nullptr;
+    ~GrBufs()
+    {
+        (void)hipFree(G); (void)hipFree(LC); (void)hipFree(cg); (void)hipFree(cc); (void)hipFree(gsize); (void)hipFree(Svar); (void)hipFree(pI);
+        (void)hipFree(cliques); (void)hipFree(sizes); (void)hipFree(cutoffs); (void)hipFree(lnf); (void)hipFree(pZ); (void)hipFree(drop);
+    }
+};
+
+struct WindowGuard {
+    pgr_window w;
+    WindowGuard() { memset(&w, 0, sizeof w); }
+    ~WindowGuard() { pgr_window_free(&w); }
+};
+
+static double now_ms()
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+extern "C" int pgr_last_timing(double *ms5)
+{
+    if (!ms5) return PWR_ERR_ARG;
+    for (int i = 0; i < 5; ++i) ms5[i] = g_ms[i];
+    return PWR_OK;
+}
+
+extern "C" void pgr_free(pgr_result *r)
+{
+    if (!r) return;
+    free(r->kept); free(r->maxcorrs); free(r->significant); free(r->sizes); free(r->cliques); free(r->cutoffs); free(r->drop_off);
+    free(r->c_groups); free(r->c_coverage);
+    memset(r, 0, sizeof *r);
+}
+
+static int refine(int rows, int width, const unsigned char *text, const double *maxcorrs_full, int von, int bis, int mincov, double cutoff,
+                  int device, pgr_result *res)
+{
+    const double t0 = now_ms();
+    WindowGuard wg;
+    int rc = pgr_read_window(rows, width, text, von, bis, &wg.w);
+    if (rc) return rc;
+    const pgr_window &win = wg.w;
+    const int W = win.width, sc = win.sc, nk = win.kept_rows;
+    const size_t V = (size_t)W * 5;
+    res->rows = rows; res->kept_rows = nk; res->width = W; res->sc = sc;
+    res->kept = (unsigned char *)malloc((size_t)rows);
+    res->maxcorrs = (double *)malloc(sizeof(double) * V);
+    if (!res->kept || !res->maxcorrs) return PWR_ERR_NOMEM;
+    memcpy(res->kept, win.kept, (size_t)rows);
+    if ((rc = pgr_slice_maxcorrs(maxcorrs_full, width * 5, win.von, win.bis, res->maxcorrs))) return rc;
+    cutoff = pgr_default_cutoff(cutoff, W);
+    res->cutoff = cutoff;
+    if ((rc = pgr_restrict_coverage(W, win.coverage, res->maxcorrs, nullptr))) return rc;
+    std::vector<int> Svar;
+    for (size_t i = 0; i < V; ++i) if (res->maxcorrs[i] > cutoff) Svar.push_back((int)i);         // RR:1647
+    const int nS = (int)Svar.size();
+    res->nsig = nS;
+    const size_t n1 = nS ? nS : 1;
+    res->significant = (int *)calloc(n1, sizeof(int)); res->sizes = (int *)calloc(n1, sizeof(int));
+    res->cliques = (int *)calloc(n1 * (PGR_MAXCLIQUE + 1), sizeof(int)); res->cutoffs = (int *)calloc(n1, sizeof(int));
+    res->drop_off = (double *)calloc(n1, sizeof(double));
+    res->c_groups = (unsigned long long *)calloc(n1 * sc, 8); res->c_coverage = (unsigned long long *)calloc(n1 * sc, 8);
+    if (!res->significant || !res->sizes || !res->cliques || !res->cutoffs || !res->drop_off || !res->c_groups || !res->c_coverage) return PWR_ERR_NOMEM;
+    g_ms[1] = g_ms[2] = g_ms[3] = g_ms[4] = 0;
+    if (nS == 0) { g_ms[0] = now_ms() - t0; return PWR_OK; }
+    memcpy(res->significant, Svar.data(), sizeof(int) * nS);
+    if (hipSetDevice(device) != hipSuccess) return PWR_ERR_DEVICE;
+    // word-major copies for the device: the threads of a wave read neighbouring variations of one word
+    std::vector<unsigned long long> Gt(V * sc), Lt((size_t)W * sc);
+    std::vector<int> gsize(V);
+    for (size_t v = 0; v < V; ++v) {
+        int g = 0;
+        for (int w = 0; w < sc; ++w) { const unsigned long long x = win.groups[v * sc + w]; Gt[(size_t)w * V + v] = x; g += __builtin_popcountll(x); }
+        gsize[v] = g;
+    }
+    for (int c = 0; c < W; ++c)
+        for (int w = 0; w < sc; ++w) Lt[(size_t)w * W + c] = win.local_coverage[(size_t)c * sc + w];
+    std::vector<double> lnf((size_t)nk + 2);
+    for (int n = 0; n < nk + 2; ++n) lnf[n] = std::lgamma(n + 1.0);
+    const int nch = (int)((V + PGR_NT - 1) / PGR_NT), ntiles = (nS + PGR_TA - 1) / PGR_TA;
+    // enough blocks to fill the device when there are few tiles of a, long slices (a better floor) when there are many
+    int want = std::max(1, std::min(PGR_MAXSLICES, (2048 + ntiles - 1) / ntiles));
+    want = std::min(want, nch);
+    const int cps = (nch + want - 1) / want, nslices = (nch + cps - 1) / cps;
+    GrBufs d;
+    const size_t np = (size_t)nS * nslices * PGR_KEEP;
+    if (hipMalloc(&d.G, V * sc * 8) != hipSuccess || hipMalloc(&d.LC, (size_t)W * sc * 8) != hipSuccess || hipMalloc(&d.gsize, V * 4) != hipSuccess ||
+        hipMalloc(&d.Svar, (size_t)nS * 4) != hipSuccess || hipMalloc(&d.lnf, lnf.size() * 8) != hipSuccess || hipMalloc(&d.pZ, np * 8) != hipSuccess ||
+        hipMalloc(&d.pI, np * 4) != hipSuccess || hipMalloc(&d.cliques, (size_t)nS * (PGR_MAXCLIQUE + 1) * 4) != hipSuccess ||
+        hipMalloc(&d.sizes, (size_t)nS * 4) != hipSuccess || hipMalloc(&d.cutoffs, (size_t)nS * 4) != hipSuccess || hipMalloc(&d.drop, (size_t)nS * 8) != hipSuccess ||
+        hipMalloc(&d.cg, (size_t)nS * sc * 8) != hipSuccess || hipMalloc(&d.cc, (size_t)nS * sc * 8) != hipSuccess) return PWR_ERR_NOMEM;
+    HIPC(hipMemcpy(d.G, Gt.data(), V * sc * 8, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d.LC, Lt.data(), (size_t)W * sc * 8, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d.gsize, gsize.data(), V * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d.Svar, Svar.data(), (size_t)nS * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d.lnf, lnf.data(), lnf.size() * 8, hipMemcpyHostToDevice));
+    HIPC(hipMemset(d.cg, 0, (size_t)nS * sc * 8)); HIPC(hipMemset(d.cc, 0, (size_t)nS * sc * 8));
+    HIPC(hipDeviceSynchronize());
+    const double t1 = now_ms();
+    hipLaunchKernelGGL(k_gr_cliques, dim3(ntiles, nslices), dim3(PGR_NT), 0, 0, (int)V, W, sc, nS, d.Svar, d.G, d.LC, d.gsize, d.lnf, mincov / 4, cutoff,
+                       cps, nslices, d.pZ, d.pI);
+    HIPC(hipGetLastError());
+    HIPC(hipDeviceSynchronize());
+    const double t2 = now_ms();
+    hipLaunchKernelGGL(k_gr_votes, dim3(nS), dim3(256), 0, 0, (int)V, W, sc, nk, nslices, d.Svar, d.pZ, d.pI, d.G, d.LC, d.cliques, d.sizes, d.cutoffs,
+                       d.drop, d.cg, d.cc);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpy(res->cliques, d.cliques, (size_t)nS * (PGR_MAXCLIQUE + 1) * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(res->sizes, d.sizes, (size_t)nS * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(res->cutoffs, d.cutoffs, (size_t)nS * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(res->drop_off, d.drop, (size_t)nS * 8, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(res->c_groups, d.cg, (size_t)nS * sc * 8, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(res->c_coverage, d.cc, (size_t)nS * sc * 8, hipMemcpyDeviceToHost));
+    for (int s = 0; s < nS; ++s)
+        if (res->sizes[s] <= 5) res->maxcorrs[Svar[s]] = 0.0;                                    // RR:1686
+    const double t3 = now_ms();
+    g_ms[0] = t3 - t0; g_ms[1] = t1 - t0; g_ms[2] = t2 - t1; g_ms[3] = t3 - t2; g_ms[4] = (double)nS * (double)(V - 1);
+    return PWR_OK;
+}
+
+extern "C" int pgr_refine(int rows, int width, const unsigned char *text, const double *maxcorrs_full, int von, int bis, int mincov, double cutoff,
+                          int device, pgr_result *result)
+{
+    if (!result) return PWR_ERR_ARG;
+    memset(result, 0, sizeof *result);
+    if (rows <= 0 || width <= 0 || !text || !maxcorrs_full || mincov < 0) return PWR_ERR_ARG;
+    if (!(cutoff <= 100.0)) return PWR_ERR_ARG;                        // the trim of RR:1228-1231 needs greedy <= Best_Corrs[0] = 100
+    const int rc = refine(rows, width, text, maxcorrs_full, von, bis, mincov, cutoff, device, result);
+    if (rc) pgr_free(result);
+    return rc;
+}

@@ -25,6 +25,7 @@
 #include <cstring>
 #include <vector>
 
+#include "hyper_tail.h"
 #include "pmc.h"
 
 #define PMC_TI 16                   // variations i per tile
@@ -142,53 +143,6 @@ __global__ __launch_bounds__(256) void k_mc_end(int W, int sc, int mincov, const
         if (!s_open) break;
     }
     if (tid < PMC_EI && ii0 + tid < W) jend[ii0 + tid] = s_end[tid];
-}
-
-// lnf[n] = lgamma(n + 1), n <= rows (made on the host: no count exceeds the number of rows)
-__device__ __forceinline__ double d_lnchoose(const double *__restrict__ lnf, unsigned n, unsigned m)
-{
-    if (m == n || m == 0) return 0.0;
-    return lnf[n] - lnf[m] - lnf[n - m];
-}
-
-__device__ __forceinline__ double d_ln_hyper_pdf(const double *__restrict__ lnf, unsigned k, unsigned n1, unsigned n2, unsigned t)
-{
-    return d_lnchoose(lnf, n1, k) + d_lnchoose(lnf, n2, t - k) - d_lnchoose(lnf, n1 + n2, t);
-}
-
-__device__ __forceinline__ double d_hyper_pdf(const double *__restrict__ lnf, unsigned k, unsigned n1, unsigned n2, unsigned t)
-{
-    if (t > n1 + n2) t = n1 + n2;
-    if (k > n1 || k > t) return 0.0;
-    if (t > n2 && k + n2 < t) return 0.0;
-    return exp(d_ln_hyper_pdf(lnf, k, n1, n2, t));
-}
-
-// gsl_cdf_hypergeometric_Q(k, n1, n2, t) = P(X > k)
-__device__ double d_hyper_Q(const double *__restrict__ lnf, unsigned k, unsigned n1, unsigned n2, unsigned t)
-{
-    if (k >= n1 || k >= t) return 0.0;
-    const double midpoint = ((double)t * n1) / ((double)n1 + n2);
-    if (k < midpoint) {
-        unsigned i = k;
-        double s = d_hyper_pdf(lnf, i, n1, n2, t), P = s;
-        while (i > 0) {
-            s *= (i / (n1 - i + 1.0)) * ((n2 + i - t) / (t - i + 1.0));
-            P += s;
-            if (s / P < 2.2204460492503131e-16) break;
-            i--;
-        }
-        return 1.0 - P;
-    }
-    unsigned i = k + 1;
-    double s = d_hyper_pdf(lnf, i, n1, n2, t), Q = s;
-    while (i < t) {
-        s *= ((n1 - i) / (i + 1.0)) * ((t - i) / (n2 + i + 1.0 - t));
-        Q += s;
-        if (s / Q < 2.2204460492503131e-16) break;
-        i++;
-    }
-    return Q;
 }
 
 // MC:413-434 PositiveSignificance (not inlined: the epilogue of k_mc_pairs calls it from an unrolled loop over register arrays)

@@ -87,3 +87,11 @@ def initial_msa_from_reads(cfg: dg.SimConfig, device: int = 0, cutoff: float = 0
             "rejected_by_cutoff": classes.count("l"), "cells": st["cells"], "write_dataset_s": round(t1 - t0, 1),
             "read_cutter_s": round(t2 - t1, 2), "align_s": round(t3 - t2, 2), "build_msa_s": round(time.time() - t3, 1)}
     return rows, info
+
+
+def refined_groups(rows, von=None, bis=None, cov: int = 30, cutoff: float = 0.0, device: int = 0):
+    """The back of the chain: MaxCorrelation on the realigned MSA `rows` (MC:839-905), then RepeatResolver's group
+    refinement on the window [von, bis] (RR:3948-4024).  Returns group_refinement.RefinedGroups."""
+    from .group_refinement import refine_groups
+    from .max_correlation import max_correlations
+    return refine_groups(rows, max_correlations(rows, cov, device), von, bis, cov, cutoff, device)
