@@ -7,9 +7,14 @@
  * threads): the window reader (Einlesen, RR:293-429), the MaxCorrs slice (RR:609-646), the default cutoff and the coverage
  * restriction (RR:3977-4014), and for every significant variation its clique (Cliquer, RR:1179-1240), Sizes, the cutoff
  * of the smallest drop (Dropoff_Cutoff, RR:1460-1522) and the refined group and coverage (CliqueGroup, RR:976-1008,
- * CliqueCoverage, RR:1064-1096).  The subdivision stages that follow in the reference work on these arrays and are not
- * part of this library.  BestCutoff and KorrMaxCutoff (RR:1659-1660) are left out: their results are overwritten by
- * RR:1661 and they have no other effect.
+ * CliqueCoverage, RR:1064-1096).  BestCutoff and KorrMaxCutoff (RR:1659-1660) are left out: their results are overwritten
+ * by RR:1661 and they have no other effect.
+ *
+ * On these arrays work the first two subdivision stages (main(), RR:4026-4062), which partition the kept rows into repeat
+ * copies: DropOff_Subdivision (RR:3180-3271) and RelativeDropoff_Subdivision (RR:3274-3378) with their helpers
+ * (Unterteilungskomprimierung RR:1823-1843, UnterteilungsKomplettierung RR:1845-1865, Relative_Dropoff_Cutoff RR:2859-2920,
+ * Unterteilung_Rausschreiben RR:568-585): the lower half of this header.  Unterteilung_Assessment (RR:2824-2856) only
+ * prints and is left out.  Kmeans_Subdivision and a drop-in RepeatResolver binary are not part of this library.
  *
  * Floating point: only the ranking of the clique's candidates touches it (the hypergeometric tail, as in pmc.h: equal to
  * the reference's up to rounding, not bit for bit); everything else is integer arithmetic or one division of integers.
@@ -77,6 +82,49 @@ int pgr_read_maxcorrs_file(const char *path, int von, int bis, double **out, int
 double pgr_default_cutoff(double cutoff, int width);
 /* RR:4003-4014: zeroes maxcorrs[i] where coverage[i / 5] * 10 < maxcov * 9; *maxcov = the maximum of coverage */
 int pgr_restrict_coverage(int width, const int *coverage, double *maxcorrs, int *maxcov);
+
+/* ---- the drop-off subdivisions (RR:4026-4062) ---- */
+/* Both stages select the entries s with maxcorrs[significant[s]] > cutoff (RR:3188, RR:3281; sizecutoff = -1), constants as
+ * in main(): mingroup = mincov / 2, dropoffcutoff = 0.0001. */
+typedef struct {
+    int rows, kept_rows;
+    int dropoff_parts, reldrop_parts; /* parts after DropOff_Subdivision and after RelativeDropoff_Subdivision */
+    int selected;                     /* entries over the cutoff: `anzahl` of both stages */
+    int eligible;                     /* parts of stage 1 with more than 2 * mingroup rows (RR:3303) */
+    int *dropoff_labels;              /* [rows] after UnterteilungsKomplettierung: -1 for the rows left out */
+    int *reldrop_labels;              /* [rows] likewise */
+    int *winner;                      /* [dropoff_parts] the variation that split the part in stage 2, -1: none */
+    int *winner_cutoff;               /* [dropoff_parts] its relative cutoff c (CliqueGroup(Clique, c)), -1: none */
+} pgr_subdivision;
+
+/* Both stages on the window's Groups and the refined arrays (which are taken as they are: the refinement is not re-run, and
+ * nothing is written into them -- the reference overwrites Drop_Off[] in stage 2 (RR:2912), which nothing ported reads
+ * afterwards).  Stage 1 runs on the host, stage 2's votes on the device.  PWR_ERR_ARG: mincov < 0, rows / kept_rows / sc /
+ * width of window and result differ, or a clique that is not -1 terminated or names a variation outside the window.
+ * PWR_ERR_RANGE: more than 65535 kept rows (the kernel counts a partition's rows in 16 bits; pgr_read_window allows 30000).
+ * nsig == 0 or nothing selected: every kept row gets label 0 in both outputs and the device is not touched. */
+int pgr_subdivide(const pgr_window *win, const pgr_result *refined, int mincov, int device, pgr_subdivision *out);
+void pgr_subdivision_free(pgr_subdivision *out);
+/* Duration of the last pgr_subdivide, ms: [0] the exchange sort, [1] the rest of stage 1, [2] upload, [3] kernel, [4] apply
+ * (winners' groups, splits, renumbering).  (Kept per process, not per call.) */
+int pgr_last_subdivision_timing(double *ms5);
+
+/* ---- host side, plain C (pgr_host.c) ---- */
+/* DropOff_Subdivision (RR:3180-3271) with the exchange sort of RR:3199-3213 as it is (not stable: a library sort would
+ * change the labels): labels[kept_rows] before UnterteilungsKomplettierung, *parts their number; ms2 (may be NULL): [0] the
+ * sort, [1] the splitting loop. */
+int pgr_dropoff_subdivision(const pgr_result *refined, int mingroup, int *labels, int *parts, double *ms2);
+/* Unterteilungskomprimierung (RR:1823-1843): renumbers labels[n] by first appearance; returns the number of parts */
+int pgr_compress_labels(int n, int *labels);
+/* UnterteilungsKomplettierung (RR:1845-1865): out[rows] = the labels of the kept rows, -1 for the others */
+int pgr_complete_labels(int rows, const unsigned char *kept, const int *labels, int *out);
+/* Unterteilung_Rausschreiben (RR:568-585): decimal labels separated by '\n', no trailing newline */
+int pgr_write_subdivision(const char *path, const int *labels, int rows);
+/* The reference's file name "<stage>SubdivisionOf_<von>_<bis>_<msa>" (RR:4041-4046; stage = "Dropoff" or "RelDrop").  von
+ * and bis are the ones main() printed into von_string / bis_string (RR:3962-3965): its own variables after RR:3948-3952,
+ * so von = bis = -1 gives 0 and 1500000; Einlesen clips a copy of bis (RR:328), which does not reach the name.
+ * PWR_ERR_RANGE if buf[n] is too small. */
+int pgr_subdivision_name(char *buf, size_t n, const char *stage, int von, int bis, const char *msa);
 
 #ifdef __cplusplus
 }

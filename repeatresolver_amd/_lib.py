@@ -39,7 +39,9 @@ PMC_EXPORTS = ["pmc_maxcorrs", "pmc_last_timing", "pmc_read_msa", "pmc_write", "
 
 # every symbol include/pgr.h declares (RepeatResolver's group refinement)
 PGR_EXPORTS = ["pgr_refine", "pgr_free", "pgr_last_timing", "pgr_read_window", "pgr_window_free", "pgr_slice_maxcorrs",
-               "pgr_read_maxcorrs_file", "pgr_default_cutoff", "pgr_restrict_coverage"]
+               "pgr_read_maxcorrs_file", "pgr_default_cutoff", "pgr_restrict_coverage", "pgr_subdivide", "pgr_subdivision_free",
+               "pgr_last_subdivision_timing", "pgr_dropoff_subdivision", "pgr_compress_labels", "pgr_complete_labels",
+               "pgr_write_subdivision", "pgr_subdivision_name"]
 
 
 class PgrWindow(ctypes.Structure):
@@ -56,6 +58,13 @@ class PgrResult(ctypes.Structure):
                 ("sizes", ctypes.POINTER(ctypes.c_int)), ("cliques", ctypes.POINTER(ctypes.c_int)),
                 ("cutoffs", ctypes.POINTER(ctypes.c_int)), ("drop_off", ctypes.POINTER(ctypes.c_double)),
                 ("c_groups", ctypes.POINTER(ctypes.c_uint64)), ("c_coverage", ctypes.POINTER(ctypes.c_uint64))]
+
+
+class PgrSubdivision(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_int), ("kept_rows", ctypes.c_int), ("dropoff_parts", ctypes.c_int),
+                ("reldrop_parts", ctypes.c_int), ("selected", ctypes.c_int), ("eligible", ctypes.c_int),
+                ("dropoff_labels", ctypes.POINTER(ctypes.c_int)), ("reldrop_labels", ctypes.POINTER(ctypes.c_int)),
+                ("winner", ctypes.POINTER(ctypes.c_int)), ("winner_cutoff", ctypes.POINTER(ctypes.c_int))]
 
 
 _lib = None
@@ -206,5 +215,21 @@ def load():
     lib.pgr_default_cutoff.argtypes = [ctypes.c_double, ci]
     lib.pgr_restrict_coverage.restype = ci
     lib.pgr_restrict_coverage.argtypes = [ci, pi, pd, pi]
+    lib.pgr_subdivide.restype = ci
+    lib.pgr_subdivide.argtypes = [ctypes.POINTER(PgrWindow), ctypes.POINTER(PgrResult), ci, ci, ctypes.POINTER(PgrSubdivision)]
+    lib.pgr_subdivision_free.restype = None
+    lib.pgr_subdivision_free.argtypes = [ctypes.POINTER(PgrSubdivision)]
+    lib.pgr_last_subdivision_timing.restype = ci
+    lib.pgr_last_subdivision_timing.argtypes = [pd]
+    lib.pgr_dropoff_subdivision.restype = ci
+    lib.pgr_dropoff_subdivision.argtypes = [ctypes.POINTER(PgrResult), ci, pi, pi, pd]
+    lib.pgr_compress_labels.restype = ci
+    lib.pgr_compress_labels.argtypes = [ci, pi]
+    lib.pgr_complete_labels.restype = ci
+    lib.pgr_complete_labels.argtypes = [ci, ctypes.POINTER(ctypes.c_ubyte), pi, pi]
+    lib.pgr_write_subdivision.restype = ci
+    lib.pgr_write_subdivision.argtypes = [cp, pi, ci]
+    lib.pgr_subdivision_name.restype = ci
+    lib.pgr_subdivision_name.argtypes = [cp, ctypes.c_size_t, cp, ci, ci, cp]
     _lib = lib
     return lib

@@ -10,6 +10,8 @@
 //                 slice in LDS; the running 29th value is the floor of the tail's early-out.
 //   k_gr_votes    one work-group per significant a: merges the slices' lists into the clique, then Sizes, the vote
 //                 histogram, Dropoff_Cutoff, and the refined group / coverage, one wave ballot per 64-row word.
+//   k_gr_reldrop  RelativeDropoff_Subdivision (RR:3274-3378): one work-group per selected variation, its rows' votes
+//                 scattered into per-partition histograms in LDS; behind pgr_subdivide at the end of this file.
 // TheBestUpdater (RR:1156-1176) never displaces on equality and inserts behind equal values, and the scan ascends in i: the
 // clique is the top 29 by (Z descending, i ascending), whatever the order of evaluation.  `better` below is that key.
 // This file is compiled with -ffp-contract=off: the saturated value 97.90 + F must be one division and one addition, so
@@ -220,6 +222,88 @@ __global__ __launch_bounds__(256) void k_gr_votes(int V, int W, int sc, int nk, 
     }
 }
 
+// RelativeDropoff_Subdivision (RR:3274-3378), every (partition k, selected variation) pair in one pass.  Block = one selected
+// variation; a lane per row as in k_gr_votes.  A row's two vote counts do not depend on k (RR:2873-2880 over the first
+// Sizes members, RR:982-1001 over all of them), so they are computed once per row and scattered into the histograms of
+// the row's partition in LDS, keyed by lab[] (the index among the partitions with more than 2 * mingroup rows, -1: skip).
+// One word per (partition, vote count): the low half counts v_sizes, the high half v_all; a partition has at most nk <
+// 65536 rows (checked by the host), so no half carries into the other.  PGR_SD_TILE partitions per pass, as many passes
+// as E needs.  Per partition one thread then runs the drop loop of RR:2896-2908 in double and counts drinne / draus; a
+// (variation, c) that would split competes with an atomic minimum on (rank in the selected list) << 5 | c: the first split
+// of a partition is the only one.
+#define PGR_SD_TILE 64
+#define PGR_SD_STRIDE 33            // words per partition in LDS: odd, so the evaluating threads hit different banks
+
+__global__ __launch_bounds__(256) void k_gr_reldrop(int Vc, int sc, int nk, int E, int mingroup, const int *__restrict__ selcl,
+                                                    const int *__restrict__ selsz, const int *__restrict__ lab,
+                                                    const unsigned long long *__restrict__ G, unsigned int *__restrict__ best)
+{
+    __shared__ unsigned int s_h[PGR_SD_TILE * PGR_SD_STRIDE];
+    __shared__ int s_clique[PGR_MAXCLIQUE + 2], s_nall;
+    const int sidx = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    if (tid <= PGR_MAXCLIQUE) s_clique[tid] = selcl[(size_t)sidx * (PGR_MAXCLIQUE + 1) + tid];
+    __syncthreads();
+    if (tid == 0) {
+        int nall = 0;
+        while (nall < PGR_MAXCLIQUE && s_clique[nall] >= 0) nall++;   // RR:982-989 (the host checked the members)
+        s_nall = nall;
+    }
+    __syncthreads();
+    const int n = selsz[sidx], nall = s_nall;                          // Sizes <= nall <= 30
+    for (int p0 = 0; p0 < E; p0 += PGR_SD_TILE) {
+        const int np = min(PGR_SD_TILE, E - p0);
+        for (int t = tid; t < np * PGR_SD_STRIDE; t += 256) s_h[t] = 0u;
+        __syncthreads();
+        for (int w = wave; w < sc; w += 4) {
+            const int e = lab[w * 64 + lane] - p0;                     // lab[sc * 64], -1 beyond nk
+            const bool mine = e >= 0 && e < np;
+            if (__ballot(mine) == 0ull) continue;                      // no row of this word in this pass (the same for the wave)
+            int vs = 0, va = 0;
+            for (int m = 0; m < nall; ++m) {
+                const int b = (int)((G[(size_t)w * Vc + s_clique[m]] >> lane) & 1ull);
+                va += b;
+                vs += m < n ? b : 0;
+            }
+            if (mine) {
+                unsigned int *h = s_h + e * PGR_SD_STRIDE;
+                if (vs == va) atomicAdd(h + vs, 0x10001u);
+                else { atomicAdd(h + vs, 1u); atomicAdd(h + va, 0x10000u); }
+            }
+        }
+        __syncthreads();
+        if (tid < np) {
+            unsigned int h[32];
+            int sz[32];                                                // sizes[k] = rows of the partition in more than k groups
+#pragma unroll
+            for (int k = 0; k < 32; ++k) h[k] = s_h[tid * PGR_SD_STRIDE + k];
+            int run = 0;
+#pragma unroll
+            for (int k = 31; k >= 0; --k) { sz[k] = run; run += (int)(h[k] & 0xffffu); }
+            const int count = run;
+            int c = 1;                                                 // RR:2886-2908 with c = 0
+            double min_drop = 1000000.0;
+#pragma unroll
+            for (int i = 1; i < PGR_MAXCLIQUE - 1; ++i) {
+                if (i < n - 1) {
+                    const int m = min(nk - sz[i], sz[i]);              // RR:2898: signumber, not the partition's size
+                    if (m > 0) {
+                        const double drop = (double)(sz[i - 1] - sz[i + 1]) / (double)m;
+                        if (drop < min_drop) { min_drop = drop; c = i; }
+                    }
+                }
+            }
+            if (min_drop < 0.0001) {                                   // RR:3336
+                int drinne = 0;                                        // rows of the partition in CliqueGroup(Clique, c)
+#pragma unroll
+                for (int k = 0; k < 32; ++k) drinne += k > c ? (int)(h[k] >> 16) : 0;
+                const int draus = count - drinne;
+                if (drinne > mingroup && draus > mingroup) atomicMin(&best[p0 + tid], ((unsigned int)sidx << 5) | (unsigned int)c);
+            }
+        }
+        __syncthreads();
+    }
+}
+
 #define HIPC(call)                                                                     \
     do {                                                                               \
         hipError_t e_ = (call);                                                        \
@@ -361,5 +445,149 @@ extern "C" int pgr_refine(int rows, int width, const unsigned char *text, const 
     if (!(cutoff <= 100.0)) return PWR_ERR_ARG;                        // the trim of RR:1228-1231 needs greedy <= Best_Corrs[0] = 100
     const int rc = refine(rows, width, text, maxcorrs_full, von, bis, mincov, cutoff, device, result);
     if (rc) pgr_free(result);
+    return rc;
+}
+
+// ---- the drop-off subdivisions (RR:4026-4062) ----
+static double g_sd_ms[5] = {0, 0, 0, 0, 0};
+
+extern "C" int pgr_last_subdivision_timing(double *ms5)
+{
+    if (!ms5) return PWR_ERR_ARG;
+    for (int i = 0; i < 5; ++i) ms5[i] = g_sd_ms[i];
+    return PWR_OK;
+}
+
+extern "C" void pgr_subdivision_free(pgr_subdivision *o)
+{
+    if (!o) return;
+    free(o->dropoff_labels); free(o->reldrop_labels); free(o->winner); free(o->winner_cutoff);
+    memset(o, 0, sizeof *o);
+}
+
+struct SdBufs {
+    unsigned long long *G = nullptr;
+    int *selcl = nullptr, *selsz = nullptr, *lab = nullptr;
+    unsigned int *best = nullptr;
+    ~SdBufs() { (void)hipFree(G); (void)hipFree(selcl); (void)hipFree(selsz); (void)hipFree(lab); (void)hipFree(best); }
+};
+
+static int subdivide(const pgr_window *win, const pgr_result *r, int mincov, int device, pgr_subdivision *out)
+{
+    const int rows = win->rows, T = win->kept_rows, sc = win->sc, mingroup = mincov / 2;   // RR:4028
+    const size_t V = (size_t)win->width * 5;
+    out->rows = rows; out->kept_rows = T;
+    out->dropoff_labels = (int *)malloc(sizeof(int) * (size_t)(rows ? rows : 1));
+    out->reldrop_labels = (int *)malloc(sizeof(int) * (size_t)(rows ? rows : 1));
+    if (!out->dropoff_labels || !out->reldrop_labels) return PWR_ERR_NOMEM;
+    for (int i = 0; i < 5; ++i) g_sd_ms[i] = 0;
+    // the selected entries, ascending (RR:3279-3286), and their cliques: -1 terminated within 31 entries, members inside the window
+    std::vector<int> sel;
+    for (int s = 0; s < r->nsig; ++s) {
+        const int v = r->significant[s];
+        if (v < 0 || (size_t)v >= V) return PWR_ERR_ARG;
+        if (!(r->maxcorrs[v] > r->cutoff && r->sizes[s] > -1)) continue;
+        const int *cl = r->cliques + (size_t)s * (PGR_MAXCLIQUE + 1);
+        int nall = 0;
+        while (nall <= PGR_MAXCLIQUE && cl[nall] >= 0) { if ((size_t)cl[nall] >= V) return PWR_ERR_ARG; nall++; }
+        if (nall > PGR_MAXCLIQUE || r->sizes[s] > nall) return PWR_ERR_ARG;
+        sel.push_back(s);
+    }
+    const int nsel = (int)sel.size();
+    out->selected = nsel;
+    std::vector<int> U((size_t)T + 1);
+    double ms2[2] = {0, 0};
+    int number = 0;
+    int rc = pgr_dropoff_subdivision(r, mingroup, U.data(), &number, ms2);                   // RR:4037
+    if (rc) return rc;
+    g_sd_ms[0] = ms2[0]; g_sd_ms[1] = ms2[1];
+    if ((rc = pgr_complete_labels(rows, win->kept, U.data(), out->dropoff_labels))) return rc;   // RR:4047
+    number = pgr_compress_labels(T, U.data());                                               // RR:3288
+    if (number < 0) return number;
+    out->dropoff_parts = number;
+    const size_t n1 = number ? number : 1;
+    out->winner = (int *)malloc(sizeof(int) * n1); out->winner_cutoff = (int *)malloc(sizeof(int) * n1);
+    if (!out->winner || !out->winner_cutoff) return PWR_ERR_NOMEM;
+    for (size_t k = 0; k < n1; ++k) out->winner[k] = out->winner_cutoff[k] = -1;
+    // the partitions that can split at all (RR:3300-3303), numbered 0 .. E - 1 for the device
+    std::vector<int> count(n1, 0), eidx(n1, -1), part;
+    for (int j = 0; j < T; ++j) count[U[j]]++;
+    for (int k = 0; k < number; ++k)
+        if (count[k] > mingroup * 2) { eidx[k] = (int)part.size(); part.push_back(k); }
+    const int E = (int)part.size();
+    out->eligible = E;
+    std::vector<unsigned int> best((size_t)(E ? E : 1), 0xffffffffu);
+    if (nsel > 0 && E > 0) {
+        const double t0 = now_ms();
+        if (T > 65535) return PWR_ERR_RANGE;                           // the kernel's 16-bit halves (pgr_read_window allows 30 000)
+        if (hipSetDevice(device) != hipSuccess) return PWR_ERR_DEVICE;
+        // only the variations that are members of a selected clique go to the device, word-major as in pgr_refine
+        std::vector<int> col(V, -1), used;
+        std::vector<int> selcl((size_t)nsel * (PGR_MAXCLIQUE + 1), -1), selsz(nsel);
+        for (int q = 0; q < nsel; ++q) {
+            const int *cl = r->cliques + (size_t)sel[q] * (PGR_MAXCLIQUE + 1);
+            for (int m = 0; m <= PGR_MAXCLIQUE && cl[m] >= 0; ++m) {
+                if (col[cl[m]] < 0) { col[cl[m]] = (int)used.size(); used.push_back(cl[m]); }
+                selcl[(size_t)q * (PGR_MAXCLIQUE + 1) + m] = col[cl[m]];
+            }
+            selsz[q] = r->sizes[sel[q]];
+        }
+        const size_t Vc = used.size();
+        std::vector<unsigned long long> Gt((Vc ? Vc : 1) * sc);
+        for (size_t c = 0; c < Vc; ++c)
+            for (int w = 0; w < sc; ++w) Gt[(size_t)w * Vc + c] = win->groups[(size_t)used[c] * sc + w];
+        std::vector<int> lab((size_t)sc * 64, -1);
+        for (int j = 0; j < T; ++j) lab[j] = eidx[U[j]];
+        SdBufs d;
+        if (hipMalloc(&d.G, Gt.size() * 8) != hipSuccess || hipMalloc(&d.selcl, selcl.size() * 4) != hipSuccess ||
+            hipMalloc(&d.selsz, (size_t)nsel * 4) != hipSuccess || hipMalloc(&d.lab, lab.size() * 4) != hipSuccess ||
+            hipMalloc(&d.best, (size_t)E * 4) != hipSuccess) return PWR_ERR_NOMEM;
+        HIPC(hipMemcpy(d.G, Gt.data(), Gt.size() * 8, hipMemcpyHostToDevice));
+        HIPC(hipMemcpy(d.selcl, selcl.data(), selcl.size() * 4, hipMemcpyHostToDevice));
+        HIPC(hipMemcpy(d.selsz, selsz.data(), (size_t)nsel * 4, hipMemcpyHostToDevice));
+        HIPC(hipMemcpy(d.lab, lab.data(), lab.size() * 4, hipMemcpyHostToDevice));
+        HIPC(hipMemset(d.best, 0xff, (size_t)E * 4));
+        HIPC(hipDeviceSynchronize());
+        const double t1 = now_ms();
+        hipLaunchKernelGGL(k_gr_reldrop, dim3(nsel), dim3(256), 0, 0, (int)Vc, sc, T, E, mingroup, d.selcl, d.selsz, d.lab, d.G, d.best);
+        HIPC(hipGetLastError());
+        HIPC(hipDeviceSynchronize());
+        HIPC(hipMemcpy(best.data(), d.best, (size_t)E * 4, hipMemcpyDeviceToHost));
+        g_sd_ms[2] = t1 - t0; g_sd_ms[3] = now_ms() - t1;
+    }
+    const double t2 = now_ms();
+    // CliqueGroup(Clique, c) for the winners only (RR:3312), restricted to the rows of their partition, and the split (RR:3353-3362)
+    for (int e = 0; e < E; ++e) {
+        if (best[e] == 0xffffffffu) continue;
+        const int q = (int)(best[e] >> 5), c = (int)(best[e] & 31u), k = part[e];
+        if (q >= nsel) return PWR_ERR_INTERNAL;
+        const int *cl = r->cliques + (size_t)sel[q] * (PGR_MAXCLIQUE + 1);
+        for (int j = 0; j < T; ++j) {
+            if (U[j] != k) continue;
+            int ii = 0;
+            for (int m = 0; m <= PGR_MAXCLIQUE && cl[m] >= 0; ++m) ii += (int)((win->groups[(size_t)cl[m] * sc + j / 64] >> (j % 64)) & 1ull);
+            U[j] = ii > c ? number + 1 + k * 2 : number + 2 + k * 2;
+        }
+        out->winner[k] = r->significant[sel[q]];
+        out->winner_cutoff[k] = c;
+    }
+    const int after = pgr_compress_labels(T, U.data());                                      // RR:3371
+    if (after < 0) return after;
+    out->reldrop_parts = after;
+    if ((rc = pgr_complete_labels(rows, win->kept, U.data(), out->reldrop_labels))) return rc;   // RR:4061
+    g_sd_ms[4] = now_ms() - t2;
+    return PWR_OK;
+}
+
+extern "C" int pgr_subdivide(const pgr_window *win, const pgr_result *refined, int mincov, int device, pgr_subdivision *out)
+{
+    if (!out) return PWR_ERR_ARG;
+    memset(out, 0, sizeof *out);
+    if (!win || !refined || mincov < 0 || !win->kept || !win->groups) return PWR_ERR_ARG;
+    if (win->rows != refined->rows || win->kept_rows != refined->kept_rows || win->sc != refined->sc || win->width != refined->width) return PWR_ERR_ARG;
+    if (win->rows < 0 || win->kept_rows < 0 || win->kept_rows > win->rows || win->width <= 0 || win->sc != win->kept_rows / 64 + 1 || refined->nsig < 0) return PWR_ERR_ARG;
+    if (refined->nsig > 0 && (!refined->significant || !refined->maxcorrs || !refined->sizes || !refined->cliques || !refined->drop_off || !refined->c_groups)) return PWR_ERR_ARG;
+    const int rc = subdivide(win, refined, mincov, device, out);
+    if (rc) pgr_subdivision_free(out);
     return rc;
 }

@@ -1,5 +1,6 @@
 /* pgr_host.c -- host side of RepeatResolver's group refinement, plain C: the window reader, the MaxCorrs slice and the
- * preparation in main() (RR:293-429, RR:609-646, RR:3977-4014). */
+ * preparation in main() (RR:293-429, RR:609-646, RR:3977-4014); below them DropOff_Subdivision and the helpers of both
+ * drop-off subdivisions (RR:568-585, RR:1823-1865, RR:3180-3271). */
 #define _POSIX_C_SOURCE 200809L
 #include "pgr.h"
 
@@ -7,6 +8,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <time.h>
 
 static int code_of(unsigned char ch)
 {
@@ -115,5 +117,137 @@ int pgr_restrict_coverage(int width, const int *coverage, double *maxcorrs, int 
     for (size_t i = 0; i < (size_t)width * 5; i++)
         if (coverage[i / 5] * 10 < m * 9) maxcorrs[i] = 0.0;                       /* RR:4011-4014 */
     if (maxcov) *maxcov = m;
+    return PWR_OK;
+}
+
+/* ---- the drop-off subdivisions: stage 1 and the helpers of both (RR:568-585, RR:1823-1865, RR:3180-3271) ---- */
+
+static double now_ms(void)
+{
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
+}
+
+int pgr_compress_labels(int n, int *labels)
+{
+    if (n < 0 || (n > 0 && !labels)) return PWR_ERR_ARG;
+    int max = 0;
+    for (int i = 0; i < n; i++) if (max < labels[i]) max = labels[i];              /* RR:1829 */
+    int *replace = malloc(sizeof(int) * ((size_t)max + 1));
+    if (!replace) return PWR_ERR_NOMEM;
+    for (int i = 0; i < max + 1; i++) replace[i] = -1;
+    max = 0;
+    for (int i = 0; i < n; i++) {
+        if (labels[i] > -1) {                                                      /* RR:1835-1838 */
+            if (replace[labels[i]] < 0) { replace[labels[i]] = max; max++; }
+            labels[i] = replace[labels[i]];
+        }
+    }
+    free(replace);
+    return max;
+}
+
+int pgr_complete_labels(int rows, const unsigned char *kept, const int *labels, int *out)
+{
+    if (rows < 0 || !kept || !out) return PWR_ERR_ARG;
+    int j = 0;
+    for (int i = 0; i < rows; i++) {                                               /* RR:1852-1863 */
+        if (kept[i]) {
+            if (!labels) return PWR_ERR_ARG;
+            out[i] = labels[j];
+            j++;
+        } else {
+            out[i] = -1;
+        }
+    }
+    return PWR_OK;
+}
+
+int pgr_write_subdivision(const char *path, const int *labels, int rows)
+{
+    if (!path || rows < 0 || (rows > 0 && !labels)) return PWR_ERR_ARG;
+    FILE *f = fopen(path, "w");
+    if (!f) return PWR_ERR_IO;                                                     /* RR:573-577 */
+    for (int i = 0; i < rows; i++) {                                               /* RR:579-583 */
+        if (i != 0) fprintf(f, "\n");
+        fprintf(f, "%d", labels[i]);
+    }
+    if (fclose(f) != 0) return PWR_ERR_IO;
+    return PWR_OK;
+}
+
+int pgr_subdivision_name(char *buf, size_t n, const char *stage, int von, int bis, const char *msa)
+{
+    if (!buf || !stage || !msa) return PWR_ERR_ARG;
+    if (von == -1 && bis == -1) { von = 0; bis = PGR_MAX_COLUMNS; }                /* RR:3948-3952 */
+    const int len = snprintf(buf, n, "%sSubdivisionOf_%d_%d_%s", stage, von, bis, msa);   /* RR:4041-4046 */
+    if (len < 0 || (size_t)len >= n) return PWR_ERR_RANGE;
+    return PWR_OK;
+}
+
+int pgr_dropoff_subdivision(const pgr_result *r, int mingroup, int *labels, int *parts, double *ms2)
+{
+    if (!r || !parts || mingroup < 0 || r->kept_rows < 0 || r->nsig < 0 || (r->kept_rows > 0 && !labels)) return PWR_ERR_ARG;
+    if (r->nsig > 0 && (!r->significant || !r->maxcorrs || !r->sizes || !r->drop_off || !r->c_groups)) return PWR_ERR_ARG;
+    if (r->sc != r->kept_rows / 64 + 1) return PWR_ERR_ARG;
+    const double t0 = now_ms();
+    const int signumber = r->kept_rows, sc = r->sc;
+    const double dropoffcutoff = 0.0001;                                           /* RR:4036 */
+    int anzahl = 0;
+    int *I = malloc(sizeof(int) * ((size_t)r->nsig + 1));
+    if (!I) return PWR_ERR_NOMEM;
+    for (int s = 0; s < r->nsig; s++) {                                            /* RR:3186-3193, sizecutoff = -1 */
+        if (r->significant[s] < 0 || r->significant[s] >= r->width * 5) { free(I); return PWR_ERR_ARG; }
+        if (r->maxcorrs[r->significant[s]] > r->cutoff && r->sizes[s] > -1) { I[anzahl] = s; anzahl++; }
+    }
+    const double *Drop_Off = r->drop_off;
+    const int *Sizes = r->sizes;
+#define MAXCORRS(s) (r->maxcorrs[r->significant[s]])
+    int i, j, k;
+    for (i = 0; i < anzahl; i++) {                                                 /* RR:3199-3213, swap for swap */
+        for (j = i + 1; j < anzahl; j++) {
+            if (Drop_Off[I[i]] > Drop_Off[I[j]]) { k = I[i]; I[i] = I[j]; I[j] = k; }
+            else if (Drop_Off[I[i]] == Drop_Off[I[j]]) {
+                if (Sizes[I[i]] < Sizes[I[j]]) { k = I[i]; I[i] = I[j]; I[j] = k; }
+                else if (Sizes[I[i]] == Sizes[I[j]]) {
+                    if (MAXCORRS(I[i]) < MAXCORRS(I[j])) { k = I[i]; I[i] = I[j]; I[j] = k; }
+                }
+            }
+        }
+    }
+#undef MAXCORRS
+    const double t1 = now_ms();
+    for (i = 0; i < signumber; i++) labels[i] = 0;                                 /* RR:3221 */
+    int number = 1, number2 = 1, drinne, draus;
+    for (i = 0; i < anzahl; i++) {                                                 /* RR:3225-3263 */
+        if (Drop_Off[I[i]] < dropoffcutoff) {
+            const unsigned long long *cg = r->c_groups + (size_t)I[i] * sc;
+            for (k = 0; k < number; k++) {
+                drinne = 0;
+                draus = 0;
+                for (j = 0; j < signumber; j++) {
+                    if (labels[j] == k) {
+                        if ((cg[j / 64] >> (j % 64)) & 1ull) drinne += 1;
+                        else draus += 1;
+                    }
+                }
+                if (drinne > mingroup && draus > mingroup) {
+                    for (j = 0; j < signumber; j++) {
+                        if (labels[j] == k) {
+                            if ((cg[j / 64] >> (j % 64)) & 1ull) labels[j] = number2;
+                            else labels[j] = number2 + 1;
+                        }
+                    }
+                    number2 += 2;
+                }
+            }
+            number = pgr_compress_labels(signumber, labels);                       /* RR:3259-3260 */
+            if (number < 0) { free(I); return number; }
+        }
+    }
+    free(I);
+    *parts = number;
+    if (ms2) { ms2[0] = t1 - t0; ms2[1] = now_ms() - t1; }
     return PWR_OK;
 }

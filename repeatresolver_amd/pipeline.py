@@ -95,3 +95,10 @@ def refined_groups(rows, von=None, bis=None, cov: int = 30, cutoff: float = 0.0,
     from .group_refinement import refine_groups
     from .max_correlation import max_correlations
     return refine_groups(rows, max_correlations(rows, cov, device), von, bis, cov, cutoff, device)
+
+
+def subdivided(rows, von=None, bis=None, cov: int = 30, cutoff: float = 0.0, device: int = 0):
+    """refined_groups, then RepeatResolver's two drop-off subdivisions of the window's rows (RR:4026-4062).  Returns
+    subdivision.Subdivision: per input row its part after each stage (-1: the row does not span the window)."""
+    from .subdivision import subdivide
+    return subdivide(rows, refined_groups(rows, von, bis, cov, cutoff, device), von, bis, cov, device)

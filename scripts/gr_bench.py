@@ -6,7 +6,10 @@ realignment round: one JSON line.
 intersections each, and one hypergeometric tail where the intersection is large enough -- the per-pair arithmetic of
 MaxCorrelation's k_mc_pairs (scripts/mc_bench.py), whose rate on the same MSA is measured alongside as the yardstick.
 CPU baseline: the literal restatement tests/gr_checker.py on --cpu-sig significant variations of the same window (one
-core, Python: a checker, not an optimised port), whose cliques must equal the device's."""
+core, Python: a checker, not an optimised port), whose cliques must equal the device's.
+"subdivision": the two drop-off subdivisions on the same window after the refinement (include/pgr.h, pgr_subdivide): the
+exchange sort, the rest of stage 1, upload, k_gr_reldrop and the apply step, ms, and the kernel's time over k_gr_votes'
+(votes_ms, which also holds the refinement's downloads)."""
 import argparse
 import json
 import os
@@ -55,6 +58,12 @@ def main():
         res = gr.refine_groups(rows, mc, von, bis, a.cov)
         walls.append(time.time() - t0)
     tm = gr.last_timing()
+    from repeatresolver_amd import subdivision as sdv
+    for _ in range(2):
+        t0 = time.time()
+        sub = sdv.subdivide(rows, res, von, bis, a.cov)
+        sub_wall = time.time() - t0
+    st = sdv.last_timing()
     out = {"metric": "group refinement clique pairs/sec", "value": tm["pairs"] / (tm["cliques_ms"] * 1e-3), "unit": "pairs/s",
            "workload": f"{a.workload}: pipeline MSA after {a.rounds} realignment round(s), {T} rows x {W} columns; window [{von}, {bis}], "
                        f"{int(res.kept.sum())} kept rows, {len(res.significant)} significant of {res.width * 5} variations, cov {a.cov}",
@@ -63,7 +72,10 @@ def main():
            "refined": int((res.sizes > 5).sum()), "dropped": int((res.sizes <= 5).sum()),
            "k_mc_pairs_same_msa": {"pairs": mct["pairs"], "pairs_ms": round(mct["pairs_ms"], 1),
                                    "pairs_per_s": mct["pairs"] / (mct["pairs_ms"] * 1e-3)},
-           "prepare_s": round(prep_s, 1)}
+           "prepare_s": round(prep_s, 1),
+           "subdivision": {"timing_ms": {k: round(v, 3) for k, v in st.items()}, "wall_s": round(sub_wall, 3), "selected": sub.selected,
+                           "dropoff_parts": sub.dropoff_parts, "eligible": sub.eligible, "reldrop_parts": sub.reldrop_parts,
+                           "k_gr_reldrop_over_k_gr_votes": round(st["kernel_ms"] / tm["votes_ms"], 3) if tm["votes_ms"] else None}}
     if a.cpu_sig and len(res.significant):
         import gr_checker as gc
         win = gc.Window(rows, mc, von, bis, a.cov)
