@@ -1,14 +1,18 @@
 /* TEST INFRASTRUCTURE -- NOT PRODUCT CODE.
  *
- * CPU restatement of /root/reference/MaxCorrelation.c ("MC"): the step after PW_ReAligner -- for every
+ * CPU restatement of the reference's MaxCorrelation.c ("MC"): the step after PW_ReAligner -- for every
  * variation (column, symbol) of the realigned MSA the largest significance of its co-occurrence with a variation at least
  * 20 columns away (MC:745-837), written one "%f" per line (MC:516-532).
  *
- * PARITY UNPINNED: the reference needs GSL (gsl_cdf_hypergeometric_Q, MC:415), which this image does not have, so it cannot
- * be compiled here and no fixture made with it exists.  hyper_Q below restates the algorithm of GSL 2.x
- * cdf/hypergeometric.c + randist/hyperg.c (sum of pdf terms by ratio recurrences away from k, pdf = exp of three
- * lnchoose, each lgamma-based) from its published description, not from its source; results should agree with GSL to
- * about 1e-12 relative, the output has six decimals.
+ * PINNED to the unmodified reference program text, linked with a stand-in for the three GSL functions it calls
+ * (oracle/gsl_standin.c, whose hypergeometric tails are mco_hyper_Q / mco_hyper_P below): `make -C oracle ref` builds
+ * oracle/_ref/max_correlation that way, oracle/gen_rr_fixtures.py records its MaxCorrsOf_ files under tests/golden/, and
+ * tests/test_rr_reference.py compares this restatement with them.  That pins everything AROUND the tail -- the reader, the
+ * pair loop, the thresholds, the saturation branches, the "%f" writer.  The tail itself is pinned separately, against scipy
+ * and against exact rationals (tests/test_mc_oracle.py).  This is NOT parity with a GSL-linked binary: hyper_Q below
+ * restates the algorithm of GSL 2.x cdf/hypergeometric.c + randist/hyperg.c (sum of pdf terms by ratio recurrences away
+ * from k, pdf = exp of three lnchoose, each lgamma-based) from its published description, not from its source; results
+ * should agree with GSL to about 1e-12 relative, the output has six decimals.
  */
 #define _POSIX_C_SOURCE 200809L
 #include <math.h>
@@ -65,6 +69,14 @@ double mco_hyper_Q(unsigned k, unsigned n1, unsigned n2, unsigned t)            
     const double midpoint = ((double)t * n1) / ((double)n1 + n2);
     if (k < midpoint) return 1.0 - hyper_lower(k, n1, n2, t);
     return hyper_upper(k, n1, n2, t);
+}
+
+double mco_hyper_P(unsigned k, unsigned n1, unsigned n2, unsigned t)            /* gsl_cdf_hypergeometric_P: P(X <= k) */
+{
+    if (k >= n1 || k >= t) return 1.0;
+    const double midpoint = ((double)t * n1) / ((double)n1 + n2);
+    if (k < midpoint) return hyper_lower(k, n1, n2, t);
+    return 1.0 - hyper_upper(k, n1, n2, t);
 }
 
 /* MC:413-434 PositiveSignificance from the four counts and the two group sizes */

@@ -5,8 +5,10 @@ include/pgr.h covers: Einlesen (RR:293-429), the MaxCorrs slice (RR:609-646), th
 Cliquer with TheBestUpdater's insertion (RR:1156-1240), Sizes (RR:1650), Dropoff_Cutoff (RR:1460-1522), CliqueGroup
 (RR:976-1008) and CliqueCoverage (RR:1064-1096).
 
-PARITY UNPINNED against the reference itself: it needs GSL, which is not available, so it cannot be compiled.  The only
-floating point here is the hypergeometric tail, taken from mco_hyper_Q of oracle/libmcoracle.so -- the restatement that
+PINNED to the unmodified reference program text, linked with a stand-in for its three GSL functions (oracle/gsl_standin.c;
+not a GSL-linked binary): fed the reference's own MaxCorrs values, this checker and tests/sd_checker.py reproduce both label
+files the reference writes, byte for byte (tests/test_rr_reference.py).  The reference writes none of the intermediate
+arrays (cliques, sizes, groups): for those this restatement stays the yardstick.  The only floating point here is the hypergeometric tail, taken from mco_hyper_Q of oracle/libmcoracle.so -- the restatement that
 tests/test_mc_oracle.py pins against scipy and exact rationals -- followed by one log10.  Row sets are kept as 0/1
 matrices (row r = the r-th kept row), so every count is an exact integer product."""
 import ctypes

@@ -1,5 +1,7 @@
-"""-m gpu: the HIP group refinement (include/pgr.h) against the literal restatement tests/gr_checker.py.  Parity with the
-REFERENCE is unpinned (it needs GSL): see the checker's header.
+"""-m gpu: the HIP group refinement (include/pgr.h) against the literal restatement tests/gr_checker.py, for the arrays
+the reference never writes.  What it does write -- the label files that depend on these arrays -- is compared with the
+REFERENCE (the unmodified program text linked with a stand-in for its three GSL functions, not a GSL-linked binary) in
+tests/test_gpu_rr_reference.py: see the checker's header.
 
 Compared exactly: kept, sizes, cutoffs, c_groups, c_coverage, cliques and the zero pattern of maxcorrs; drop_off to 1e-12.
 The device's tail differs from the host's by rounding (the MaxCorrelation tests allow 1e-9 for it), so a variation whose

@@ -1,7 +1,8 @@
 """-m gpu: the HIP MaxCorrelation (include/pmc.h) against the CPU restatement oracle/mc_oracle.c.  Floating
 point: the significances must agree to 1e-9 (the tail sums are the same scheme, lgamma / exp / log10 differ by rounding
-between device and host); zeros and the 98 + F saturations exactly where the oracle has them.  Parity with the REFERENCE
-is unpinned (it needs GSL): see the oracle's header."""
+between device and host); zeros and the 98 + F saturations exactly where the oracle has them.  The device is compared with
+the REFERENCE's own files (the unmodified program text linked with a stand-in for its three GSL functions, not a GSL-linked
+binary) in tests/test_gpu_rr_reference.py: see the oracle's header."""
 import ctypes
 import os
 import subprocess

@@ -1,6 +1,8 @@
-"""The CPU restatement of MaxCorrelation (oracle/mc_oracle.c).  PARITY UNPINNED against the reference (it
-needs GSL, which this image lacks): what can be pinned here is the hypergeometric tail, against scipy's independent
-implementation, and the rest of the restatement against a literal numpy transcription of MC:745-837 on a small MSA."""
+"""The CPU restatement of MaxCorrelation (oracle/mc_oracle.c).  The restatement is pinned to the unmodified
+reference program text, linked with a stand-in for its three GSL functions, in tests/test_rr_reference.py (not to a
+GSL-linked binary).  Here the stand-in's hypergeometric tail -- this file's mco_hyper_Q -- is pinned separately, against
+scipy's independent implementation and against exact rationals, and the rest of the restatement against a literal numpy
+transcription of MC:745-837 on a small MSA."""
 import ctypes
 import os
 import subprocess
