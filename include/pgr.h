@@ -14,10 +14,13 @@
  * copies: DropOff_Subdivision (RR:3180-3271) and RelativeDropoff_Subdivision (RR:3274-3378) with their helpers
  * (Unterteilungskomprimierung RR:1823-1843, UnterteilungsKomplettierung RR:1845-1865, Relative_Dropoff_Cutoff RR:2859-2920,
  * Unterteilung_Rausschreiben RR:568-585): the lower half of this header.  Unterteilung_Assessment (RR:2824-2856) only
- * prints and is left out.  Kmeans_Subdivision and a drop-in RepeatResolver binary are not part of this library.
+ * prints and is left out.  The last stage, Kmeans_Subdivision (RR:3382-3403) with Relative_Vars (RR:2424-2493),
+ * Relative_Group_Significance / CumHypGeo_Log (RR:490-522) and Kmeans (RR:2604-2821), closes the header; the drop-in
+ * `RepeatResolver` binary (repeat_resolver_main.c) chains all of it and writes the reference's three label files.
  *
  * Floating point: only the ranking of the clique's candidates touches it (the hypergeometric tail, as in pmc.h: equal to
- * the reference's up to rounding, not bit for bit); everything else is integer arithmetic or one division of integers.
+ * the reference's up to rounding, not bit for bit) and, in the k-means stage, the choice of the variables (both tails, against
+ * the cutoff); everything else is integer arithmetic or one division of integers.
  * Error codes are those of pwr.h.
  */
 #ifndef PGR_H
@@ -125,6 +128,54 @@ int pgr_write_subdivision(const char *path, const int *labels, int rows);
  * so von = bis = -1 gives 0 and 1500000; Einlesen clips a copy of bis (RR:328), which does not reach the name.
  * PWR_ERR_RANGE if buf[n] is too small. */
 int pgr_subdivision_name(char *buf, size_t n, const char *stage, int von, int bis, const char *msa);
+
+/* ---- the k-means subdivision (RR:4064-4075) ---- */
+/* Kmeans_Subdivision on the labels RelativeDropoff_Subdivision left: every part with more than 2 * mingroup rows (an
+ * "eligible" part, numbered e = 0 .. eligible - 1 in ascending order of its label) gets its variables (Relative_Vars) and is
+ * clustered on them (Kmeans).  Per eligible part: */
+typedef struct {
+    int rows, kept_rows;
+    int parts_before, parts;          /* after the first and after the last Unterteilungskomprimierung (RR:3385, RR:3398) */
+    int eligible;
+    int *labels;                      /* [rows] after UnterteilungsKomplettierung: -1 for the rows left out */
+    int *part;                        /* [eligible] the part's label after RR:3385 */
+    int *part_rows;                   /* [eligible] anzahl */
+    int *row_offset;                  /* [eligible + 1] into row / cluster_before / cluster_after */
+    int *row;                         /* the kept-row indices I[] of each part, ascending */
+    int *cluster_before;              /* Clusternumber after the assignment (RR:2706-2723) */
+    int *cluster_after;               /* Clusternumber after the reassignment chain (RR:2726-2755) */
+    int *varzahl;                     /* [eligible] */
+    int *var_offset;                  /* [eligible + 1] into vars */
+    int *vars;                        /* Vars of each part, ascending */
+    long long pairs;                  /* pairs (i, j >= i + 100) evaluated by Relative_Vars, all parts */
+    /* only from pgr_kmeans_subdivide_pairs: every evaluated pair, by part, then i, then j ascending */
+    long long debug_pairs;
+    int *pair_part, *pair_i, *pair_j; /* [debug_pairs] e, i, j */
+    double *pair_z;                   /* [debug_pairs] Relative_Group_Significance(Groups[j], Groups[i], U) */
+} pgr_kmeans;
+
+/* win and refined as for pgr_subdivide (of refined only kept, maxcorrs and cutoff are read); reldrop_labels_rows[rows] =
+ * pgr_subdivision.reldrop_labels (-1 for the rows left out).  The relative significance of every pair and the O(rows^2)
+ * passes of Kmeans (centroids, assignment, the scores the chain reads) run on the device; the chain itself walks a
+ * device-made matrix of 16-bit scores on the host.  PWR_ERR_ARG: as pgr_subdivide, or a label below -1 / a kept row labelled
+ * -1.  PWR_ERR_RANGE: more than 65535 eligible parts, an eligible part with more than 65471 variables (a score would not fit
+ * 16 bits), or the score matrices
+ * of all eligible parts together beyond 2^28 entries (only where the chain runs: mincov > 5).  No eligible part: the device
+ * is not touched and labels are the compressed input. */
+int pgr_kmeans_subdivide(const pgr_window *win, const pgr_result *refined, const int *reldrop_labels_rows, int mincov, int device,
+                         pgr_kmeans *out);
+void pgr_kmeans_free(pgr_kmeans *out);
+/* The same, and every evaluated pair's Z in out->pair_* (for tests; PWR_ERR_RANGE beyond 2^24 pairs or matrix entries) */
+int pgr_kmeans_subdivide_pairs(const pgr_window *win, const pgr_result *refined, const int *reldrop_labels_rows, int mincov, int device,
+                               pgr_kmeans *out);
+/* Duration of the last pgr_kmeans_subdivide, ms: [0] all, [1] upload + counts |G & U|, [2] the significance kernel, [3]
+ * centroids + assignment + scores, [4] the chain on the host; [5] pairs evaluated.  (Kept per process, not per call.) */
+int pgr_last_kmeans_timing(double *ms6);
+
+/* ---- host side, plain C (pgr_host.c) ---- */
+/* The reassignment chain of Kmeans (RR:2726-2755), literally: scores[i * anzahl + j] = GrMatch(Centroids[j], VarSigs[i]),
+ * clusternumber[anzahl] in place (entries in [0, anzahl): PWR_ERR_ARG otherwise).  mingroup <= 2: nothing moves. */
+int pgr_kmeans_reassign(int anzahl, const unsigned short *scores, int mingroup, int *clusternumber);
 
 #ifdef __cplusplus
 }

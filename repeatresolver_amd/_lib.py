@@ -41,7 +41,8 @@ PMC_EXPORTS = ["pmc_maxcorrs", "pmc_last_timing", "pmc_read_msa", "pmc_write", "
 PGR_EXPORTS = ["pgr_refine", "pgr_free", "pgr_last_timing", "pgr_read_window", "pgr_window_free", "pgr_slice_maxcorrs",
                "pgr_read_maxcorrs_file", "pgr_default_cutoff", "pgr_restrict_coverage", "pgr_subdivide", "pgr_subdivision_free",
                "pgr_last_subdivision_timing", "pgr_dropoff_subdivision", "pgr_compress_labels", "pgr_complete_labels",
-               "pgr_write_subdivision", "pgr_subdivision_name"]
+               "pgr_write_subdivision", "pgr_subdivision_name", "pgr_kmeans_subdivide", "pgr_kmeans_free", "pgr_kmeans_subdivide_pairs",
+               "pgr_last_kmeans_timing", "pgr_kmeans_reassign"]
 
 
 class PgrWindow(ctypes.Structure):
@@ -65,6 +66,18 @@ class PgrSubdivision(ctypes.Structure):
                 ("reldrop_parts", ctypes.c_int), ("selected", ctypes.c_int), ("eligible", ctypes.c_int),
                 ("dropoff_labels", ctypes.POINTER(ctypes.c_int)), ("reldrop_labels", ctypes.POINTER(ctypes.c_int)),
                 ("winner", ctypes.POINTER(ctypes.c_int)), ("winner_cutoff", ctypes.POINTER(ctypes.c_int))]
+
+
+class PgrKmeans(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_int), ("kept_rows", ctypes.c_int), ("parts_before", ctypes.c_int), ("parts", ctypes.c_int),
+                ("eligible", ctypes.c_int), ("labels", ctypes.POINTER(ctypes.c_int)), ("part", ctypes.POINTER(ctypes.c_int)),
+                ("part_rows", ctypes.POINTER(ctypes.c_int)), ("row_offset", ctypes.POINTER(ctypes.c_int)),
+                ("row", ctypes.POINTER(ctypes.c_int)), ("cluster_before", ctypes.POINTER(ctypes.c_int)),
+                ("cluster_after", ctypes.POINTER(ctypes.c_int)), ("varzahl", ctypes.POINTER(ctypes.c_int)),
+                ("var_offset", ctypes.POINTER(ctypes.c_int)), ("vars", ctypes.POINTER(ctypes.c_int)), ("pairs", ctypes.c_longlong),
+                ("debug_pairs", ctypes.c_longlong), ("pair_part", ctypes.POINTER(ctypes.c_int)),
+                ("pair_i", ctypes.POINTER(ctypes.c_int)), ("pair_j", ctypes.POINTER(ctypes.c_int)),
+                ("pair_z", ctypes.POINTER(ctypes.c_double))]
 
 
 _lib = None
@@ -231,5 +244,15 @@ def load():
     lib.pgr_write_subdivision.argtypes = [cp, pi, ci]
     lib.pgr_subdivision_name.restype = ci
     lib.pgr_subdivision_name.argtypes = [cp, ctypes.c_size_t, cp, ci, ci, cp]
+    lib.pgr_kmeans_subdivide.restype = ci
+    lib.pgr_kmeans_subdivide.argtypes = [ctypes.POINTER(PgrWindow), ctypes.POINTER(PgrResult), pi, ci, ci, ctypes.POINTER(PgrKmeans)]
+    lib.pgr_kmeans_free.restype = None
+    lib.pgr_kmeans_free.argtypes = [ctypes.POINTER(PgrKmeans)]
+    lib.pgr_kmeans_subdivide_pairs.restype = ci
+    lib.pgr_kmeans_subdivide_pairs.argtypes = lib.pgr_kmeans_subdivide.argtypes
+    lib.pgr_last_kmeans_timing.restype = ci
+    lib.pgr_last_kmeans_timing.argtypes = [pd]
+    lib.pgr_kmeans_reassign.restype = ci
+    lib.pgr_kmeans_reassign.argtypes = [ci, ctypes.POINTER(ctypes.c_ushort), ci, pi]
     _lib = lib
     return lib

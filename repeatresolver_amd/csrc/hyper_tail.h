@@ -53,4 +53,32 @@ static __device__ double d_hyper_Q(const double *__restrict__ lnf, unsigned k, u
     return Q;
 }
 
+// gsl_cdf_hypergeometric_P(k, n1, n2, t) = P(X <= k): the same two sums, the other way round (used by the k-means stage's
+// relative significance only, RR:492)
+[[maybe_unused]] static __device__ double d_hyper_P(const double *__restrict__ lnf, unsigned k, unsigned n1, unsigned n2, unsigned t)
+{
+    if (k >= n1 || k >= t) return 1.0;
+    const double midpoint = ((double)t * n1) / ((double)n1 + n2);
+    if (k < midpoint) {
+        unsigned i = k;
+        double s = d_hyper_pdf(lnf, i, n1, n2, t), P = s;
+        while (i > 0) {
+            s *= (i / (n1 - i + 1.0)) * ((n2 + i - t) / (t - i + 1.0));
+            P += s;
+            if (s / P < 2.2204460492503131e-16) break;
+            i--;
+        }
+        return P;
+    }
+    unsigned i = k + 1;
+    double s = d_hyper_pdf(lnf, i, n1, n2, t), Q = s;
+    while (i < t) {
+        s *= ((n1 - i) / (i + 1.0)) * ((t - i) / (n2 + i + 1.0 - t));
+        Q += s;
+        if (s / Q < 2.2204460492503131e-16) break;
+        i++;
+    }
+    return 1.0 - Q;
+}
+
 #endif /* PWR_HYPER_TAIL_H */

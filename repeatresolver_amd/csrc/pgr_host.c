@@ -1,6 +1,6 @@
 /* pgr_host.c -- host side of RepeatResolver's group refinement, plain C: the window reader, the MaxCorrs slice and the
  * preparation in main() (RR:293-429, RR:609-646, RR:3977-4014); below them DropOff_Subdivision and the helpers of both
- * drop-off subdivisions (RR:568-585, RR:1823-1865, RR:3180-3271). */
+ * drop-off subdivisions (RR:568-585, RR:1823-1865, RR:3180-3271); at the end the reassignment chain of Kmeans (RR:2726-2755). */
 #define _POSIX_C_SOURCE 200809L
 #include "pgr.h"
 
@@ -249,5 +249,38 @@ int pgr_dropoff_subdivision(const pgr_result *r, int mingroup, int *labels, int 
     free(I);
     *parts = number;
     if (ms2) { ms2[0] = t1 - t0; ms2[1] = now_ms() - t1; }
+    return PWR_OK;
+}
+
+/* ---- the k-means subdivision: the sequential chain (RR:2726-2755) ---- */
+
+int pgr_kmeans_reassign(int anzahl, const unsigned short *scores, int mingroup, int *clusternumber)
+{
+    if (anzahl < 0 || (anzahl > 0 && (!scores || !clusternumber))) return PWR_ERR_ARG;
+    int *Clustersize = calloc((size_t)anzahl + 1, sizeof(int));
+    if (!Clustersize) return PWR_ERR_NOMEM;
+    int i, j, min;
+    for (i = 0; i < anzahl; i++) {
+        if (clusternumber[i] < 0 || clusternumber[i] >= anzahl) { free(Clustersize); return PWR_ERR_ARG; }
+        Clustersize[clusternumber[i]]++;                                           /* RR:2722 */
+    }
+    for (min = 2; min < mingroup; min++) {
+        for (i = 0; i < anzahl; i++) {
+            if (Clustersize[clusternumber[i]] <= min) {                            /* RR:2731 */
+                const unsigned short *row = scores + (size_t)i * anzahl;
+                int best_score = 0, best_j = 0;
+                for (j = 0; j < anzahl; j++) {
+                    if (Clustersize[j] >= min && clusternumber[i] != j) {          /* RR:2737 */
+                        const int score = row[j];
+                        if (score > best_score && i != j) { best_score = score; best_j = j; }
+                    }
+                }
+                Clustersize[clusternumber[i]]--;                                   /* RR:2747-2749 */
+                clusternumber[i] = best_j;
+                Clustersize[best_j]++;
+            }
+        }
+    }
+    free(Clustersize);
     return PWR_OK;
 }

@@ -102,3 +102,13 @@ def subdivided(rows, von=None, bis=None, cov: int = 30, cutoff: float = 0.0, dev
     subdivision.Subdivision: per input row its part after each stage (-1: the row does not span the window)."""
     from .subdivision import subdivide
     return subdivide(rows, refined_groups(rows, von, bis, cov, cutoff, device), von, bis, cov, device)
+
+
+def clustered(rows, von=None, bis=None, cov: int = 30, cutoff: float = 0.0, device: int = 0):
+    """subdivided, then RepeatResolver's k-means subdivision (RR:4064-4075): the whole tool.  Returns (subdivision.Subdivision,
+    kmeans_subdivision.KmeansSubdivision); the second's labels are the final partition of the rows into repeat copies."""
+    from .kmeans_subdivision import kmeans_subdivide
+    from .subdivision import subdivide
+    refined = refined_groups(rows, von, bis, cov, cutoff, device)
+    sub = subdivide(rows, refined, von, bis, cov, device)
+    return sub, kmeans_subdivide(rows, refined, sub, von, bis, cov, device)

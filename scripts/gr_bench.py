@@ -9,7 +9,9 @@ CPU baseline: the literal restatement tests/gr_checker.py on --cpu-sig significa
 core, Python: a checker, not an optimised port), whose cliques must equal the device's.
 "subdivision": the two drop-off subdivisions on the same window after the refinement (include/pgr.h, pgr_subdivide): the
 exchange sort, the rest of stage 1, upload, k_gr_reldrop and the apply step, ms, and the kernel's time over k_gr_votes'
-(votes_ms, which also holds the refinement's downloads)."""
+(votes_ms, which also holds the refinement's downloads).
+"kmeans": the last stage on the same window (pgr_kmeans_subdivide): counts, the significance kernel k_km_pairs, the k-means
+kernels and the host chain, ms, and k_km_pairs' pairs/s (a pair is evaluated from both of its sides) beside k_mc_pairs'."""
 import argparse
 import json
 import os
@@ -64,6 +66,12 @@ def main():
         sub = sdv.subdivide(rows, res, von, bis, a.cov)
         sub_wall = time.time() - t0
     st = sdv.last_timing()
+    from repeatresolver_amd import kmeans_subdivision as kmv
+    for _ in range(2):
+        t0 = time.time()
+        kms = kmv.kmeans_subdivide(rows, res, sub, von, bis, a.cov)
+        km_wall = time.time() - t0
+    kt = kmv.last_timing()
     out = {"metric": "group refinement clique pairs/sec", "value": tm["pairs"] / (tm["cliques_ms"] * 1e-3), "unit": "pairs/s",
            "workload": f"{a.workload}: pipeline MSA after {a.rounds} realignment round(s), {T} rows x {W} columns; window [{von}, {bis}], "
                        f"{int(res.kept.sum())} kept rows, {len(res.significant)} significant of {res.width * 5} variations, cov {a.cov}",
@@ -75,7 +83,10 @@ def main():
            "prepare_s": round(prep_s, 1),
            "subdivision": {"timing_ms": {k: round(v, 3) for k, v in st.items()}, "wall_s": round(sub_wall, 3), "selected": sub.selected,
                            "dropoff_parts": sub.dropoff_parts, "eligible": sub.eligible, "reldrop_parts": sub.reldrop_parts,
-                           "k_gr_reldrop_over_k_gr_votes": round(st["kernel_ms"] / tm["votes_ms"], 3) if tm["votes_ms"] else None}}
+                           "k_gr_reldrop_over_k_gr_votes": round(st["kernel_ms"] / tm["votes_ms"], 3) if tm["votes_ms"] else None},
+           "kmeans": {"timing_ms": {k: round(v, 3) for k, v in kt.items() if k != "pairs"}, "wall_s": round(km_wall, 3), "eligible": kms.eligible,
+                      "parts": kms.parts, "varzahl": [len(v) for v in kms.vars][:16], "pairs": kt["pairs"],
+                      "k_km_pairs_per_s": kt["pairs"] / (kt["pairs_ms"] * 1e-3) if kt["pairs_ms"] else None}}
     if a.cpu_sig and len(res.significant):
         import gr_checker as gc
         win = gc.Window(rows, mc, von, bis, a.cov)
