@@ -18,6 +18,10 @@
  * Relative_Group_Significance / CumHypGeo_Log (RR:490-522) and Kmeans (RR:2604-2821), closes the header; the drop-in
  * `RepeatResolver` binary (repeat_resolver_main.c) chains all of it and writes the reference's three label files.
  *
+ * At the end: the whole repeat.  pgr_msa_* keep the MSA on the device, read every window there (pgr_win_device.hip) and run
+ * the three stages per window in one call; pgr_connect chains the windows' labellings into the connection matrix of the
+ * reference's SimDataAssessment.py (ProbabilityMatrix, MultiStepResolution: "SDA:" 359-391).
+ *
  * Floating point: only the ranking of the clique's candidates touches it (the hypergeometric tail, as in pmc.h: equal to
  * the reference's up to rounding, not bit for bit) and, in the k-means stage, the choice of the variables (both tails, against
  * the cutoff); everything else is integer arithmetic or one division of integers.
@@ -176,6 +180,63 @@ int pgr_last_kmeans_timing(double *ms6);
 /* The reassignment chain of Kmeans (RR:2726-2755), literally: scores[i * anzahl + j] = GrMatch(Centroids[j], VarSigs[i]),
  * clusternumber[anzahl] in place (entries in [0, anzahl): PWR_ERR_ARG otherwise).  mingroup <= 2: nothing moves. */
 int pgr_kmeans_reassign(int anzahl, const unsigned short *scores, int mingroup, int *clusternumber);
+
+/* ---- the whole repeat: several windows of one MSA (the reference README's `-f x y`, `-f y z`, ... and their connection) ---- */
+/* The MSA resident on the device: text = rows x width characters, uploaded once.  Limits and errors as pgr_read_window;
+ * PWR_ERR_NOMEM when the device (or the host) cannot hold it.  Every index into the text is 64-bit. */
+typedef struct pgr_msa pgr_msa;
+int pgr_msa_open(int rows, int width, const unsigned char *text, int device, pgr_msa **h);
+void pgr_msa_close(pgr_msa *h);
+/* Einlesen (RR:293-429) on the device copy (pgr_win_device.hip): *win and the return code are what pgr_read_window gives
+ * for the same text, von and bis, bit for bit (von = bis = -1 and the clipping of bis included).  Release *win with
+ * pgr_window_free. */
+int pgr_msa_window(pgr_msa *h, int von, int bis, pgr_window *win);
+
+/* One window of a resolution: what the three stages leave for [von, bis] */
+typedef struct {
+    int von, bis;                     /* as given: sites[p], sites[p + 1] */
+    int kept_rows;
+    int dropoff_parts, reldrop_parts, kmeans_parts;
+    double cutoff;                    /* the one used (RR:3977) */
+    int *dropoff_labels;              /* [rows] -1 for the rows left out */
+    int *reldrop_labels;              /* [rows] */
+    int *kmeans_labels;               /* [rows] */
+} pgr_resolved_window;
+
+typedef struct {
+    int rows, nwindows;
+    pgr_resolved_window *windows;     /* [nwindows] */
+} pgr_resolution;
+
+/* Window p = [sites[p], sites[p + 1]], both ends inclusive, p = 0 .. nsites - 2: every window is read on the device
+ * (pgr_msa_window's kernels) and goes through the arithmetic of pgr_refine, pgr_subdivide and pgr_kmeans_subdivide.  The
+ * refinement reads the sets the reader left on the device; the window is downloaded once for the host parts of the other two
+ * stages, which run through their entry points above.  maxcorrs_full[width * 5], mincov and cutoff as for pgr_refine.
+ * PWR_ERR_ARG: nsites < 2, sites not strictly increasing or negative; any other failure is the failing stage's code, and
+ * *out is then empty. */
+int pgr_msa_resolve(pgr_msa *h, const double *maxcorrs_full, int nsites, const int *sites, int mincov, double cutoff,
+                    pgr_resolution *out);
+void pgr_resolution_free(pgr_resolution *out);
+/* Duration of the last pgr_msa_resolve and of the pgr_msa_open before it, ms: [0] the upload of the text (pgr_msa_open),
+ * [1] all of pgr_msa_resolve, and summed over its windows [2] the reader kernels (with the kept-row list), [3] the download of
+ * the window, [4] the refinement, [5] the subdivisions, [6] the k-means stage.  (Kept per process, not per call.) */
+int pgr_last_resolve_timing(double *ms7);
+
+/* ---- host side, plain C (pgr_host.c): the connection of the windows (SimDataAssessment.py:359-391, "SDA:") ---- */
+typedef struct {
+    int k_first, k_last;              /* parts of the first and of the last labelling: max label + 1 */
+    double *matrix;                   /* [k_first][k_last] AllConCon after the normalisation (SDA:384-391) */
+    int *best;                        /* [k_first] the first column with the largest value above 0.0 (SDA:399-405); -1: a zero row */
+    double *confidence;               /* [k_first] the value there; 0.0 for a zero row */
+    int *mutual;                      /* [k_first] 1: that value is also the maximum of its column */
+} pgr_connection;
+
+/* ProbabilityMatrix (SDA:359-370) between neighbours of labels[nres][rows] (-1: the row is not in that labelling), the
+ * forward matrices multiplied left to right, the backward ones (of the reversed list) likewise, connection = forward x
+ * transposed backward elementwise, every row divided by its sum where that is > 0 (SDA:372-391); all in doubles.  nres = 2:
+ * one matrix each way.  PWR_ERR_ARG: nres < 2, rows <= 0, a label below -1, a labelling without a label >= 0. */
+int pgr_connect(int nres, int rows, const int *labels, pgr_connection *out);
+void pgr_connection_free(pgr_connection *out);
 
 #ifdef __cplusplus
 }

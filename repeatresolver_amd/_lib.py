@@ -42,7 +42,8 @@ PGR_EXPORTS = ["pgr_refine", "pgr_free", "pgr_last_timing", "pgr_read_window", "
                "pgr_read_maxcorrs_file", "pgr_default_cutoff", "pgr_restrict_coverage", "pgr_subdivide", "pgr_subdivision_free",
                "pgr_last_subdivision_timing", "pgr_dropoff_subdivision", "pgr_compress_labels", "pgr_complete_labels",
                "pgr_write_subdivision", "pgr_subdivision_name", "pgr_kmeans_subdivide", "pgr_kmeans_free", "pgr_kmeans_subdivide_pairs",
-               "pgr_last_kmeans_timing", "pgr_kmeans_reassign"]
+               "pgr_last_kmeans_timing", "pgr_kmeans_reassign", "pgr_msa_open", "pgr_msa_close", "pgr_msa_window", "pgr_msa_resolve",
+               "pgr_resolution_free", "pgr_last_resolve_timing", "pgr_connect", "pgr_connection_free"]
 
 
 class PgrWindow(ctypes.Structure):
@@ -78,6 +79,23 @@ class PgrKmeans(ctypes.Structure):
                 ("debug_pairs", ctypes.c_longlong), ("pair_part", ctypes.POINTER(ctypes.c_int)),
                 ("pair_i", ctypes.POINTER(ctypes.c_int)), ("pair_j", ctypes.POINTER(ctypes.c_int)),
                 ("pair_z", ctypes.POINTER(ctypes.c_double))]
+
+
+class PgrResolvedWindow(ctypes.Structure):
+    _fields_ = [("von", ctypes.c_int), ("bis", ctypes.c_int), ("kept_rows", ctypes.c_int), ("dropoff_parts", ctypes.c_int),
+                ("reldrop_parts", ctypes.c_int), ("kmeans_parts", ctypes.c_int), ("cutoff", ctypes.c_double),
+                ("dropoff_labels", ctypes.POINTER(ctypes.c_int)), ("reldrop_labels", ctypes.POINTER(ctypes.c_int)),
+                ("kmeans_labels", ctypes.POINTER(ctypes.c_int))]
+
+
+class PgrResolution(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_int), ("nwindows", ctypes.c_int), ("windows", ctypes.POINTER(PgrResolvedWindow))]
+
+
+class PgrConnection(ctypes.Structure):
+    _fields_ = [("k_first", ctypes.c_int), ("k_last", ctypes.c_int), ("matrix", ctypes.POINTER(ctypes.c_double)),
+                ("best", ctypes.POINTER(ctypes.c_int)), ("confidence", ctypes.POINTER(ctypes.c_double)),
+                ("mutual", ctypes.POINTER(ctypes.c_int))]
 
 
 _lib = None
@@ -254,5 +272,21 @@ def load():
     lib.pgr_last_kmeans_timing.argtypes = [pd]
     lib.pgr_kmeans_reassign.restype = ci
     lib.pgr_kmeans_reassign.argtypes = [ci, ctypes.POINTER(ctypes.c_ushort), ci, pi]
+    lib.pgr_msa_open.restype = ci
+    lib.pgr_msa_open.argtypes = [ci, ci, vp, ci, ctypes.POINTER(vp)]
+    lib.pgr_msa_close.restype = None
+    lib.pgr_msa_close.argtypes = [vp]
+    lib.pgr_msa_window.restype = ci
+    lib.pgr_msa_window.argtypes = [vp, ci, ci, ctypes.POINTER(PgrWindow)]
+    lib.pgr_msa_resolve.restype = ci
+    lib.pgr_msa_resolve.argtypes = [vp, pd, ci, pi, ci, ctypes.c_double, ctypes.POINTER(PgrResolution)]
+    lib.pgr_resolution_free.restype = None
+    lib.pgr_resolution_free.argtypes = [ctypes.POINTER(PgrResolution)]
+    lib.pgr_last_resolve_timing.restype = ci
+    lib.pgr_last_resolve_timing.argtypes = [pd]
+    lib.pgr_connect.restype = ci
+    lib.pgr_connect.argtypes = [ci, ci, pi, ctypes.POINTER(PgrConnection)]
+    lib.pgr_connection_free.restype = None
+    lib.pgr_connection_free.argtypes = [ctypes.POINTER(PgrConnection)]
     _lib = lib
     return lib

@@ -29,6 +29,7 @@
 
 #include "hyper_tail.h"
 #include "pgr.h"
+#include "pgr_internal.h"
 
 #define PGR_TA 16                   // significant variations a per tile
 #define PGR_NT 256                  // threads per block = variations i per chunk
@@ -314,14 +315,21 @@ __global__ __launch_bounds__(256) void k_gr_reldrop(int Vc, int sc, int nk, int 
     } while (0)
 
 struct GrBufs {
-    unsigned long long *G = nullptr, *LC = nullptr, *cg = nullptr, *cc = nullptr;
-    int *gsize = nullptr, *Svar = nullptr, *pI = nullptr, *cliques = nullptr, *sizes = nullptr, *cutoffs = nullptr;
+    unsigned long long *cg = nullptr, *cc = nullptr;
+    int *Svar = nullptr, *pI = nullptr, *cliques = nullptr, *sizes = nullptr, *cutoffs = nullptr;
     double *lnf = nullptr, *pZ = nullptr, *drop = nullptr;
     ~GrBufs()
     {
-        (void)hipFree(G); (void)hipFree(LC); (void)hipFree(cg); (void)hipFree(cc); (void)hipFree(gsize); (void)hipFree(Svar); (void)hipFree(pI);
+        (void)hipFree(cg); (void)hipFree(cc); (void)hipFree(Svar); (void)hipFree(pI);
         (void)hipFree(cliques); (void)hipFree(sizes); (void)hipFree(cutoffs); (void)hipFree(lnf); (void)hipFree(pZ); (void)hipFree(drop);
     }
+};
+
+// the sets of pgr_refine's own window, uploaded from the host reader's
+struct GrSets {
+    unsigned long long *G = nullptr, *LC = nullptr;
+    int *gsize = nullptr;
+    ~GrSets() { (void)hipFree(G); (void)hipFree(LC); (void)hipFree(gsize); }
 };
 
 struct WindowGuard {
@@ -350,6 +358,79 @@ extern "C" void pgr_free(pgr_result *r)
     memset(r, 0, sizeof *r);
 }
 
+// The host part in front of the kernels (RR:3977-4014, RR:1647): the MaxCorrs slice, the cutoff, the coverage restriction, the
+// significant variations, and res's arrays (zeroed).
+static int refine_prepare(int rows, int nk, int W, int sc, int von, int bis, const unsigned char *kept, const int *coverage,
+                          const double *maxcorrs_full, int msa_width, double *cutoff, pgr_result *res, std::vector<int> &Svar)
+{
+    const size_t V = (size_t)W * 5;
+    res->rows = rows; res->kept_rows = nk; res->width = W; res->sc = sc;
+    res->kept = (unsigned char *)malloc((size_t)rows);
+    res->maxcorrs = (double *)malloc(sizeof(double) * V);
+    if (!res->kept || !res->maxcorrs) return PWR_ERR_NOMEM;
+    memcpy(res->kept, kept, (size_t)rows);
+    int rc;
+    if ((rc = pgr_slice_maxcorrs(maxcorrs_full, msa_width * 5, von, bis, res->maxcorrs))) return rc;
+    *cutoff = pgr_default_cutoff(*cutoff, W);
+    res->cutoff = *cutoff;
+    if ((rc = pgr_restrict_coverage(W, coverage, res->maxcorrs, nullptr))) return rc;
+    for (size_t i = 0; i < V; ++i) if (res->maxcorrs[i] > *cutoff) Svar.push_back((int)i);         // RR:1647
+    const int nS = (int)Svar.size();
+    res->nsig = nS;
+    const size_t n1 = nS ? nS : 1;
+    res->significant = (int *)calloc(n1, sizeof(int)); res->sizes = (int *)calloc(n1, sizeof(int));
+    res->cliques = (int *)calloc(n1 * (PGR_MAXCLIQUE + 1), sizeof(int)); res->cutoffs = (int *)calloc(n1, sizeof(int));
+    res->drop_off = (double *)calloc(n1, sizeof(double));
+    res->c_groups = (unsigned long long *)calloc(n1 * sc, 8); res->c_coverage = (unsigned long long *)calloc(n1 * sc, 8);
+    if (!res->significant || !res->sizes || !res->cliques || !res->cutoffs || !res->drop_off || !res->c_groups || !res->c_coverage) return PWR_ERR_NOMEM;
+    if (nS) memcpy(res->significant, Svar.data(), sizeof(int) * nS);
+    return PWR_OK;
+}
+
+// The kernels, on sets that are on the device (the current one): fills res's arrays; ms2: cliques, votes
+static int refine_on_device(const unsigned long long *dG, const unsigned long long *dLC, const int *dgsize, int nk, int W, int sc,
+                            const std::vector<int> &Svar, int mincov, double cutoff, pgr_result *res, double *ms2)
+{
+    const size_t V = (size_t)W * 5;
+    const int nS = (int)Svar.size();
+    std::vector<double> lnf((size_t)nk + 2);
+    for (int n = 0; n < nk + 2; ++n) lnf[n] = std::lgamma(n + 1.0);
+    const int nch = (int)((V + PGR_NT - 1) / PGR_NT), ntiles = (nS + PGR_TA - 1) / PGR_TA;
+    // enough blocks to fill the device when there are few tiles of a, long slices (a better floor) when there are many
+    int want = std::max(1, std::min(PGR_MAXSLICES, (2048 + ntiles - 1) / ntiles));
+    want = std::min(want, nch);
+    const int cps = (nch + want - 1) / want, nslices = (nch + cps - 1) / cps;
+    GrBufs d;
+    const size_t np = (size_t)nS * nslices * PGR_KEEP;
+    if (hipMalloc(&d.Svar, (size_t)nS * 4) != hipSuccess || hipMalloc(&d.lnf, lnf.size() * 8) != hipSuccess || hipMalloc(&d.pZ, np * 8) != hipSuccess ||
+        hipMalloc(&d.pI, np * 4) != hipSuccess || hipMalloc(&d.cliques, (size_t)nS * (PGR_MAXCLIQUE + 1) * 4) != hipSuccess ||
+        hipMalloc(&d.sizes, (size_t)nS * 4) != hipSuccess || hipMalloc(&d.cutoffs, (size_t)nS * 4) != hipSuccess || hipMalloc(&d.drop, (size_t)nS * 8) != hipSuccess ||
+        hipMalloc(&d.cg, (size_t)nS * sc * 8) != hipSuccess || hipMalloc(&d.cc, (size_t)nS * sc * 8) != hipSuccess) return PWR_ERR_NOMEM;
+    HIPC(hipMemcpy(d.Svar, Svar.data(), (size_t)nS * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d.lnf, lnf.data(), lnf.size() * 8, hipMemcpyHostToDevice));
+    HIPC(hipMemset(d.cg, 0, (size_t)nS * sc * 8)); HIPC(hipMemset(d.cc, 0, (size_t)nS * sc * 8));
+    HIPC(hipDeviceSynchronize());
+    const double t1 = now_ms();
+    hipLaunchKernelGGL(k_gr_cliques, dim3(ntiles, nslices), dim3(PGR_NT), 0, 0, (int)V, W, sc, nS, d.Svar, dG, dLC, dgsize, d.lnf, mincov / 4, cutoff,
+                       cps, nslices, d.pZ, d.pI);
+    HIPC(hipGetLastError());
+    HIPC(hipDeviceSynchronize());
+    const double t2 = now_ms();
+    hipLaunchKernelGGL(k_gr_votes, dim3(nS), dim3(256), 0, 0, (int)V, W, sc, nk, nslices, d.Svar, d.pZ, d.pI, dG, dLC, d.cliques, d.sizes, d.cutoffs,
+                       d.drop, d.cg, d.cc);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpy(res->cliques, d.cliques, (size_t)nS * (PGR_MAXCLIQUE + 1) * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(res->sizes, d.sizes, (size_t)nS * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(res->cutoffs, d.cutoffs, (size_t)nS * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(res->drop_off, d.drop, (size_t)nS * 8, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(res->c_groups, d.cg, (size_t)nS * sc * 8, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(res->c_coverage, d.cc, (size_t)nS * sc * 8, hipMemcpyDeviceToHost));
+    for (int s = 0; s < nS; ++s)
+        if (res->sizes[s] <= 5) res->maxcorrs[Svar[s]] = 0.0;                                    // RR:1686
+    ms2[0] = t2 - t1; ms2[1] = now_ms() - t2;
+    return PWR_OK;
+}
+
 static int refine(int rows, int width, const unsigned char *text, const double *maxcorrs_full, int von, int bis, int mincov, double cutoff,
                   int device, pgr_result *res)
 {
@@ -360,28 +441,11 @@ static int refine(int rows, int width, const unsigned char *text, const double *
     const pgr_window &win = wg.w;
     const int W = win.width, sc = win.sc, nk = win.kept_rows;
     const size_t V = (size_t)W * 5;
-    res->rows = rows; res->kept_rows = nk; res->width = W; res->sc = sc;
-    res->kept = (unsigned char *)malloc((size_t)rows);
-    res->maxcorrs = (double *)malloc(sizeof(double) * V);
-    if (!res->kept || !res->maxcorrs) return PWR_ERR_NOMEM;
-    memcpy(res->kept, win.kept, (size_t)rows);
-    if ((rc = pgr_slice_maxcorrs(maxcorrs_full, width * 5, win.von, win.bis, res->maxcorrs))) return rc;
-    cutoff = pgr_default_cutoff(cutoff, W);
-    res->cutoff = cutoff;
-    if ((rc = pgr_restrict_coverage(W, win.coverage, res->maxcorrs, nullptr))) return rc;
     std::vector<int> Svar;
-    for (size_t i = 0; i < V; ++i) if (res->maxcorrs[i] > cutoff) Svar.push_back((int)i);         // RR:1647
+    if ((rc = refine_prepare(rows, nk, W, sc, win.von, win.bis, win.kept, win.coverage, maxcorrs_full, width, &cutoff, res, Svar))) return rc;
     const int nS = (int)Svar.size();
-    res->nsig = nS;
-    const size_t n1 = nS ? nS : 1;
-    res->significant = (int *)calloc(n1, sizeof(int)); res->sizes = (int *)calloc(n1, sizeof(int));
-    res->cliques = (int *)calloc(n1 * (PGR_MAXCLIQUE + 1), sizeof(int)); res->cutoffs = (int *)calloc(n1, sizeof(int));
-    res->drop_off = (double *)calloc(n1, sizeof(double));
-    res->c_groups = (unsigned long long *)calloc(n1 * sc, 8); res->c_coverage = (unsigned long long *)calloc(n1 * sc, 8);
-    if (!res->significant || !res->sizes || !res->cliques || !res->cutoffs || !res->drop_off || !res->c_groups || !res->c_coverage) return PWR_ERR_NOMEM;
     g_ms[1] = g_ms[2] = g_ms[3] = g_ms[4] = 0;
     if (nS == 0) { g_ms[0] = now_ms() - t0; return PWR_OK; }
-    memcpy(res->significant, Svar.data(), sizeof(int) * nS);
     if (hipSetDevice(device) != hipSuccess) return PWR_ERR_DEVICE;
     // word-major copies for the device: the threads of a wave read neighbouring variations of one word
     std::vector<unsigned long long> Gt(V * sc), Lt((size_t)W * sc);
@@ -393,46 +457,16 @@ static int refine(int rows, int width, const unsigned char *text, const double *
     }
     for (int c = 0; c < W; ++c)
         for (int w = 0; w < sc; ++w) Lt[(size_t)w * W + c] = win.local_coverage[(size_t)c * sc + w];
-    std::vector<double> lnf((size_t)nk + 2);
-    for (int n = 0; n < nk + 2; ++n) lnf[n] = std::lgamma(n + 1.0);
-    const int nch = (int)((V + PGR_NT - 1) / PGR_NT), ntiles = (nS + PGR_TA - 1) / PGR_TA;
-    // enough blocks to fill the device when there are few tiles of a, long slices (a better floor) when there are many
-    int want = std::max(1, std::min(PGR_MAXSLICES, (2048 + ntiles - 1) / ntiles));
-    want = std::min(want, nch);
-    const int cps = (nch + want - 1) / want, nslices = (nch + cps - 1) / cps;
-    GrBufs d;
-    const size_t np = (size_t)nS * nslices * PGR_KEEP;
-    if (hipMalloc(&d.G, V * sc * 8) != hipSuccess || hipMalloc(&d.LC, (size_t)W * sc * 8) != hipSuccess || hipMalloc(&d.gsize, V * 4) != hipSuccess ||
-        hipMalloc(&d.Svar, (size_t)nS * 4) != hipSuccess || hipMalloc(&d.lnf, lnf.size() * 8) != hipSuccess || hipMalloc(&d.pZ, np * 8) != hipSuccess ||
-        hipMalloc(&d.pI, np * 4) != hipSuccess || hipMalloc(&d.cliques, (size_t)nS * (PGR_MAXCLIQUE + 1) * 4) != hipSuccess ||
-        hipMalloc(&d.sizes, (size_t)nS * 4) != hipSuccess || hipMalloc(&d.cutoffs, (size_t)nS * 4) != hipSuccess || hipMalloc(&d.drop, (size_t)nS * 8) != hipSuccess ||
-        hipMalloc(&d.cg, (size_t)nS * sc * 8) != hipSuccess || hipMalloc(&d.cc, (size_t)nS * sc * 8) != hipSuccess) return PWR_ERR_NOMEM;
-    HIPC(hipMemcpy(d.G, Gt.data(), V * sc * 8, hipMemcpyHostToDevice));
-    HIPC(hipMemcpy(d.LC, Lt.data(), (size_t)W * sc * 8, hipMemcpyHostToDevice));
-    HIPC(hipMemcpy(d.gsize, gsize.data(), V * 4, hipMemcpyHostToDevice));
-    HIPC(hipMemcpy(d.Svar, Svar.data(), (size_t)nS * 4, hipMemcpyHostToDevice));
-    HIPC(hipMemcpy(d.lnf, lnf.data(), lnf.size() * 8, hipMemcpyHostToDevice));
-    HIPC(hipMemset(d.cg, 0, (size_t)nS * sc * 8)); HIPC(hipMemset(d.cc, 0, (size_t)nS * sc * 8));
-    HIPC(hipDeviceSynchronize());
-    const double t1 = now_ms();
-    hipLaunchKernelGGL(k_gr_cliques, dim3(ntiles, nslices), dim3(PGR_NT), 0, 0, (int)V, W, sc, nS, d.Svar, d.G, d.LC, d.gsize, d.lnf, mincov / 4, cutoff,
-                       cps, nslices, d.pZ, d.pI);
-    HIPC(hipGetLastError());
-    HIPC(hipDeviceSynchronize());
-    const double t2 = now_ms();
-    hipLaunchKernelGGL(k_gr_votes, dim3(nS), dim3(256), 0, 0, (int)V, W, sc, nk, nslices, d.Svar, d.pZ, d.pI, d.G, d.LC, d.cliques, d.sizes, d.cutoffs,
-                       d.drop, d.cg, d.cc);
-    HIPC(hipGetLastError());
-    HIPC(hipMemcpy(res->cliques, d.cliques, (size_t)nS * (PGR_MAXCLIQUE + 1) * 4, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(res->sizes, d.sizes, (size_t)nS * 4, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(res->cutoffs, d.cutoffs, (size_t)nS * 4, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(res->drop_off, d.drop, (size_t)nS * 8, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(res->c_groups, d.cg, (size_t)nS * sc * 8, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(res->c_coverage, d.cc, (size_t)nS * sc * 8, hipMemcpyDeviceToHost));
-    for (int s = 0; s < nS; ++s)
-        if (res->sizes[s] <= 5) res->maxcorrs[Svar[s]] = 0.0;                                    // RR:1686
+    GrSets s;
+    if (hipMalloc(&s.G, V * sc * 8) != hipSuccess || hipMalloc(&s.LC, (size_t)W * sc * 8) != hipSuccess || hipMalloc(&s.gsize, V * 4) != hipSuccess)
+        return PWR_ERR_NOMEM;
+    HIPC(hipMemcpy(s.G, Gt.data(), V * sc * 8, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(s.LC, Lt.data(), (size_t)W * sc * 8, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(s.gsize, gsize.data(), V * 4, hipMemcpyHostToDevice));
+    double ms2[2] = {0, 0};
+    if ((rc = refine_on_device(s.G, s.LC, s.gsize, nk, W, sc, Svar, mincov, cutoff, res, ms2))) return rc;
     const double t3 = now_ms();
-    g_ms[0] = t3 - t0; g_ms[1] = t1 - t0; g_ms[2] = t2 - t1; g_ms[3] = t3 - t2; g_ms[4] = (double)nS * (double)(V - 1);
+    g_ms[0] = t3 - t0; g_ms[2] = ms2[0]; g_ms[3] = ms2[1]; g_ms[1] = g_ms[0] - ms2[0] - ms2[1]; g_ms[4] = (double)nS * (double)(V - 1);
     return PWR_OK;
 }
 
@@ -446,6 +480,27 @@ extern "C" int pgr_refine(int rows, int width, const unsigned char *text, const 
     const int rc = refine(rows, width, text, maxcorrs_full, von, bis, mincov, cutoff, device, result);
     if (rc) pgr_free(result);
     return rc;
+}
+
+int pgr_refine_sets(const pgr_device_sets *sets, const unsigned char *kept, const int *coverage, const double *maxcorrs_full, int msa_width,
+                    int mincov, double cutoff, int device, pgr_result *result, double *ms2)
+{
+    if (!result) return PWR_ERR_ARG;
+    memset(result, 0, sizeof *result);
+    if (ms2) ms2[0] = ms2[1] = 0;
+    if (!sets || !kept || !coverage || !maxcorrs_full || mincov < 0 || !sets->G || !sets->LC || !sets->gsize) return PWR_ERR_ARG;
+    if (!(cutoff <= 100.0)) return PWR_ERR_ARG;
+    std::vector<int> Svar;
+    int rc = refine_prepare(sets->rows, sets->kept_rows, sets->width, sets->sc, sets->von, sets->bis, kept, coverage, maxcorrs_full, msa_width,
+                            &cutoff, result, Svar);
+    double ms[2] = {0, 0};
+    if (!rc && !Svar.empty()) {
+        if (hipSetDevice(device) != hipSuccess) rc = PWR_ERR_DEVICE;
+        else rc = refine_on_device(sets->G, sets->LC, sets->gsize, sets->kept_rows, sets->width, sets->sc, Svar, mincov, cutoff, result, ms);
+    }
+    if (rc) { pgr_free(result); return rc; }
+    if (ms2) { ms2[0] = ms[0]; ms2[1] = ms[1]; }
+    return PWR_OK;
 }
 
 // ---- the drop-off subdivisions (RR:4026-4062) ----

@@ -284,3 +284,112 @@ int pgr_kmeans_reassign(int anzahl, const unsigned short *scores, int mingroup, 
     free(Clustersize);
     return PWR_OK;
 }
+
+/* ---- the connection of the windows (SimDataAssessment.py:359-391, "SDA:") ---- */
+
+void pgr_connection_free(pgr_connection *c)
+{
+    if (!c) return;
+    free(c->matrix); free(c->best); free(c->confidence); free(c->mutual);
+    memset(c, 0, sizeof *c);
+}
+
+/* ProbabilityMatrix (SDA:359-370): *out is calloc'ed [*k1][*k2] */
+static int probability_matrix(int rows, const int *r1, const int *r2, int k1, int k2, double **out)
+{
+    double *m = calloc((size_t)k1 * k2, sizeof(double));
+    int *sums = calloc((size_t)k1, sizeof(int));
+    if (!m || !sums) { free(m); free(sums); return PWR_ERR_NOMEM; }
+    for (int t = 0; t < rows; t++) {
+        if (r1[t] > -1 && r2[t] > -1) { sums[r1[t]]++; m[(size_t)r1[t] * k2 + r2[t]] += 1.0; }   /* SDA:361-364 */
+    }
+    for (int a = 0; a < k1; a++)
+        for (int b = 0; b < k2; b++)
+            if (sums[a] > 0) m[(size_t)a * k2 + b] /= (double)sums[a];                            /* SDA:365-368 */
+    free(sums);
+    *out = m;
+    return PWR_OK;
+}
+
+/* acc[n][k] . m[k][p], the sum over k ascending */
+static double *product(const double *acc, const double *m, int n, int k, int p)
+{
+    double *o = calloc((size_t)n * p, sizeof(double));
+    if (!o) return NULL;
+    for (int i = 0; i < n; i++)
+        for (int l = 0; l < k; l++) {
+            const double x = acc[(size_t)i * k + l];
+            if (x == 0.0) continue;                                                   /* adds +0.0: no value changes */
+            for (int j = 0; j < p; j++) o[(size_t)i * p + j] += x * m[(size_t)l * p + j];
+        }
+    return o;
+}
+
+/* the chain PM(order[0], order[1]) . PM(order[1], order[2]) ... over the labellings in the given order (SDA:376-383) */
+static int chained(int nres, int rows, const int *labels, const int *K, int backward, double **out)
+{
+    double *acc = NULL;
+    for (int s = 0; s + 1 < nres; s++) {
+        const int a = backward ? nres - 1 - s : s, b = backward ? nres - 2 - s : s + 1, first = backward ? nres - 1 : 0;
+        double *m = NULL;
+        const int rc = probability_matrix(rows, labels + (size_t)a * rows, labels + (size_t)b * rows, K[a], K[b], &m);
+        if (rc) { free(acc); return rc; }
+        if (!acc) { acc = m; continue; }
+        double *next = product(acc, m, K[first], K[a], K[b]);
+        free(acc); free(m);
+        if (!next) return PWR_ERR_NOMEM;
+        acc = next;
+    }
+    *out = acc;
+    return PWR_OK;
+}
+
+int pgr_connect(int nres, int rows, const int *labels, pgr_connection *out)
+{
+    if (!out) return PWR_ERR_ARG;
+    memset(out, 0, sizeof *out);
+    if (nres < 2 || rows <= 0 || !labels) return PWR_ERR_ARG;
+    int *K = malloc(sizeof(int) * (size_t)nres);
+    if (!K) return PWR_ERR_NOMEM;
+    for (int r = 0; r < nres; r++) {
+        int max = -1;
+        for (int t = 0; t < rows; t++) {
+            const int l = labels[(size_t)r * rows + t];
+            if (l < -1) { free(K); return PWR_ERR_ARG; }
+            if (l > max) max = l;
+        }
+        if (max < 0) { free(K); return PWR_ERR_ARG; }
+        K[r] = max + 1;
+    }
+    const int k1 = K[0], k2 = K[nres - 1];
+    double *fw = NULL, *bw = NULL;
+    int rc = chained(nres, rows, labels, K, 0, &fw);                                  /* [k1][k2] */
+    if (!rc) rc = chained(nres, rows, labels, K, 1, &bw);                             /* [k2][k1] */
+    free(K);
+    out->k_first = k1; out->k_last = k2;
+    out->best = malloc(sizeof(int) * (size_t)k1);
+    out->confidence = malloc(sizeof(double) * (size_t)k1);
+    out->mutual = malloc(sizeof(int) * (size_t)k1);
+    if (!rc && (!out->best || !out->confidence || !out->mutual)) rc = PWR_ERR_NOMEM;
+    if (rc) { free(fw); free(bw); pgr_connection_free(out); return rc; }
+    for (int a = 0; a < k1; a++) {
+        double summe = 0.0;
+        for (int b = 0; b < k2; b++) { fw[(size_t)a * k2 + b] *= bw[(size_t)b * k1 + a]; summe += fw[(size_t)a * k2 + b]; }   /* SDA:384, 388 */
+        if (summe > 0.0)
+            for (int b = 0; b < k2; b++) fw[(size_t)a * k2 + b] /= summe;             /* SDA:389-391 */
+    }
+    free(bw);
+    out->matrix = fw;
+    for (int a = 0; a < k1; a++) {
+        double maxi = 0.0;
+        int maxtt = -1;
+        for (int b = 0; b < k2; b++)
+            if (fw[(size_t)a * k2 + b] > maxi) { maxi = fw[(size_t)a * k2 + b]; maxtt = b; }   /* SDA:399-405 */
+        out->best[a] = maxtt; out->confidence[a] = maxi; out->mutual[a] = 0;
+        if (maxtt < 0) continue;
+        int is_max = 1;
+        for (int t = 0; t < k1; t++) if (fw[(size_t)t * k2 + maxtt] > maxi) is_max = 0;
+        out->mutual[a] = is_max;
+    }
+    return PWR_OK;
+}

@@ -1,0 +1,21 @@
+/* pgr_internal.h -- what pgr_device.hip and pgr_win_device.hip share inside libpwr.so; not part of the C ABI. */
+#ifndef PGR_INTERNAL_H
+#define PGR_INTERNAL_H
+
+#include "pgr.h"
+
+/* A window's sets on the device, word-major as k_gr_cliques and k_gr_votes read them */
+typedef struct {
+    int rows, kept_rows, von, bis, width, sc;
+    const unsigned long long *G;      /* [sc][width * 5] */
+    const unsigned long long *LC;     /* [sc][width] */
+    const int *gsize;                 /* [width * 5] rows of every group */
+} pgr_device_sets;
+
+/* pgr_refine from the MaxCorrs slice on, on sets that are on the device already; kept[rows] and coverage[width] on the
+ * host.  msa_width = the width of the whole MSA (maxcorrs_full[msa_width * 5]).  *result as pgr_refine leaves it (freed on
+ * failure); ms2 (may be NULL): [0] cliques, [1] votes. */
+__attribute__((visibility("hidden"))) int pgr_refine_sets(const pgr_device_sets *sets, const unsigned char *kept, const int *coverage,
+                                                          const double *maxcorrs_full, int msa_width, int mincov, double cutoff, int device,
+                                                          pgr_result *result, double *ms2);
+#endif

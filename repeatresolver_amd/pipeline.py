@@ -112,3 +112,19 @@ def clustered(rows, von=None, bis=None, cov: int = 30, cutoff: float = 0.0, devi
     refined = refined_groups(rows, von, bis, cov, cutoff, device)
     sub = subdivide(rows, refined, von, bis, cov, device)
     return sub, kmeans_subdivide(rows, refined, sub, von, bis, cov, device)
+
+
+def resolved(rows, parts: int = 6, coverage: float = 0.90, cov: int = 30, cutoff: float = 0.0, device: int = 0):
+    """The whole repeat as the reference README runs it: MaxCorrelation, Window.py's boundaries (`parts` windows over the
+    columns covered by at least `coverage` of the mean), RepeatResolver on every window [b_p, b_{p+1}] from one device copy
+    of the MSA, and the connection of the windows' k-means labellings.  Returns (boundaries, [resolution.ResolvedWindow],
+    resolution.Connection or None for a single window)."""
+    from .max_correlation import max_correlations
+    from .resolution import connect, open_msa, resolve
+    from .window import window_boundaries
+    sites = window_boundaries(rows, coverage, parts)
+    mc = max_correlations(rows, cov, device)
+    with open_msa(rows, device) as msa:
+        windows = resolve(msa, mc, sites, cov, cutoff)
+    con = connect([w.kmeans_labels for w in windows]) if len(windows) > 1 else None
+    return sites, windows, con
