@@ -1379,19 +1379,29 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
     uint32_t *dirs = jb.dirs + (size_t)job * jb.dirstride + (size_t)(seg_xb >> 4) * RS;
     unsigned *lastM = jb.lastM + (size_t)job * jb.NC;
     const int lc = lane * C;
+    // The row is carried as N(x,y) = M(x,y) - G(y): a strip's constants are turned once, here, into what a
+    // cell adds to N -- S_b(y) - G(y) + G(y-1) for the diagonal (G(y-1): the lane's column before, the left lane's last one,
+    // GL for the strip's first column), up(y) for the column itself; INF - G(y) is "unreachable" as N.  The columns past hi
+    // keep their sentinels as they are: nothing is added to them, so nothing wraps.
 #define V4_LOADS(MSX, SLOT, AU, AG, AI, GL)                                                      \
     {                                                                                            \
-        _Pragma("unroll") for (int i = 0; i < C; ++i) {                                          \
-            const int y_ = lo + (MSX) * MS + lc + i;                                             \
-            int4 p_ = make_int4(PWR_BIG / 2, PWR_BIG / 2, PWR_BIG / 2, PWR_BIG / 2);             \
-            int4 q_ = make_int4(PWR_BIG / 2, 0, PWR_BIG / 2, 0);                                 \
-            if (y_ <= hi) { p_ = rec2[2 * (y_ - lo)]; q_ = rec2[2 * (y_ - lo) + 1]; }            \
-            ldsS1[lw][SLOT][0][lc + i] = p_.x; ldsS1[lw][SLOT][1][lc + i] = p_.y;                        \
-            ldsS1[lw][SLOT][2][lc + i] = p_.z; ldsS1[lw][SLOT][3][lc + i] = p_.w;                        \
-            AU[i] = q_.x; AG[i] = q_.y; AI[i] = q_.z;                                            \
-        }                                                                                        \
         const int yq_ = lo + (MSX) * MS - 1;                                                     \
         GL = (yq_ >= lo && yq_ <= hi) ? UNI(rec2[2 * (yq_ - lo) + 1].y) : 0;                     \
+        int4 p_[C];                                                                              \
+        _Pragma("unroll") for (int i = 0; i < C; ++i) {                                          \
+            const int y_ = lo + (MSX) * MS + lc + i;                                             \
+            p_[i] = make_int4(PWR_BIG / 2, PWR_BIG / 2, PWR_BIG / 2, PWR_BIG / 2);               \
+            int4 q_ = make_int4(PWR_BIG / 2, 0, PWR_BIG / 2, 0);                                 \
+            if (y_ <= hi) { p_[i] = rec2[2 * (y_ - lo)]; q_ = rec2[2 * (y_ - lo) + 1]; }         \
+            AU[i] = q_.x + q_.y; AG[i] = q_.y; AI[i] = q_.z;                                     \
+        }                                                                                        \
+        const int gl0_ = __builtin_amdgcn_update_dpp(GL, AG[C - 1], DPP_WAVE_SHR1, 0xF, 0xF, false);   \
+        _Pragma("unroll") for (int i = 0; i < C; ++i) {                                          \
+            const int y_ = lo + (MSX) * MS + lc + i;                                             \
+            const int gp_ = y_ <= hi ? (i ? AG[i > 0 ? i - 1 : 0] : gl0_) : 0;                   \
+            ldsS1[lw][SLOT][0][lc + i] = p_[i].x + gp_; ldsS1[lw][SLOT][1][lc + i] = p_[i].y + gp_;      \
+            ldsS1[lw][SLOT][2][lc + i] = p_[i].z + gp_; ldsS1[lw][SLOT][3][lc + i] = p_[i].w + gp_;      \
+        }                                                                                        \
     }
 
     int ug[C], gg[C], ig[C];
@@ -1415,9 +1425,9 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
     // column lies left of the first row's band (a run of blanks in the row): then the free start it is.
     const int src_prev = (seg_xb > 0 && jb.src_start) ? UNI(way[-1]) : -1;
     const int src_c = src_prev >= max(0, UNI(way[0]) - H) ? src_prev : -1;
-    unsigned Mprev[C], accA[C], accC[C];
+    unsigned Mprev[C], accA[C], accC[C];                                          // Mprev holds N = M - G: score 0 is -G, unreachable INF - G
 #pragma unroll
-    for (int i = 0; i < C; ++i) { Mprev[i] = (src_c < 0 || lo + ms * MS + lc + i == src_c) ? 0u : PWR_INF; accA[i] = accC[i] = 0; }
+    for (int i = 0; i < C; ++i) { Mprev[i] = (unsigned)((src_c < 0 || lo + ms * MS + lc + i == src_c) ? -gg[i] : ig[i]); accA[i] = accC[i] = 0; }
     int gacc = -1, nacc = 0;
     int ran_prev = 0;
     int x = 0, blk = 0;
@@ -1437,7 +1447,7 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
         unsigned *cv_ = (XNEXT) == chkA ? chk_w : chk_t;                                         \
         _Pragma("unroll") for (int i = 0; i < C; ++i) {                                          \
             const int y_ = lo + ms * MS + lc + i;                                                \
-            cv_[wave * MS + lc + i] = (y_ >= (AF) && y_ < (BEND)) ? Mprev[i] : 0xffffffffu;      \
+            cv_[wave * MS + lc + i] = (y_ >= (AF) && y_ < (BEND)) ? (unsigned)gg[i] + Mprev[i] : 0xffffffffu;   /* true scores: G + N */ \
         }                                                                                        \
     }
 #define V4_ALIGN_ACC(WANT)                                                                       \
@@ -1563,8 +1573,8 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
                     if (dead) break;
                     const int eTx = (int)UNI((unsigned)eT);
 #pragma unroll
-                    for (int i = 0; i < C; ++i) Mprev[i] = (unsigned)(gg[i] + eTx);
-                    mlast_v = yq < a_prev ? PWR_INF : (needM ? UNI((unsigned)eM) : (unsigned)(gleft + eTx));
+                    for (int i = 0; i < C; ++i) Mprev[i] = (unsigned)eTx;          // N of the extension G + Ptot
+                    mlast_v = yq < a_prev ? PWR_INF - (unsigned)gleft : (needM ? UNI((unsigned)eM) : (unsigned)eTx);
                     ran_prev = 1;
                 } else if ((bMm >> (x & 63)) & 1ull) {
                     const unsigned tagp = tagbase | (unsigned)x;
@@ -1655,7 +1665,7 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
                         int af = 0, bend = 0;
                         if (CLS >= 2) af = __builtin_amdgcn_readlane(g_af, r);
                         if (CLS == 1 || CLS == 3 || CLS == 4) bend = __builtin_amdgcn_readlane(g_be, r);
-                        const int Mleft_v = bM ? (int)mlast_v : (int)PWR_INF;
+                        const int Mleft_v = bM ? (int)mlast_v : (int)PWR_INF - gleft;
                         const int pm1_0 = __builtin_amdgcn_update_dpp(Mleft_v, (int)Mprev[C - 1], DPP_WAVE_SHR1, 0xF, 0xF, false);
                         int tg[C];
                         int run = FBIG;
@@ -1724,7 +1734,8 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
                         for (int i = 0; i < C; ++i) {
                             if (BITS) accA[i] = acc_push(accA[i], __builtin_amdgcn_sicmp(tg[i], p, ICMP_SGE));
                             p = min(p, tg[i]);
-                            Mprev[i] = min((unsigned)(gg[i] + p), PWR_INF);
+                            // N = p: no band guard, so p <= tg[i] <= ig[i] already; behind a guard tg[i] may be FBIG
+                            Mprev[i] = (unsigned)(CLS == 0 ? p : min(p, ig[i]));
                         }
                         mlast_v = (unsigned)fM;
                         if (lane == 63) {
@@ -1740,7 +1751,8 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
                                 // (sc1 as the agent-scope atomic stores have it: the words must be seen by the other work-groups)
                                 // (and the wait states a store of more than 64 bits needs before a VALU may overwrite its data
                                 // registers: the compiler inserts them for its own stores, not behind inline assembly)
-                                asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(gq0 + 2 * r), "v"(w4_) : "memory");
+                                // (the group's base is wave-uniform: scalar base + the row's byte offset, one move instead of 64-bit address arithmetic)
+                                asm volatile("global_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" :: "v"(16 * r), "v"(w4_), "s"(gq0) : "memory");
                             }
                         }
                     };
@@ -1951,14 +1963,14 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
             if (dead) break;
         }
         int Mleft = (int)PWR_INF;
-        if (x == 0) Mleft = (src_c < 0 || yq == src_c) ? 0 : (int)PWR_INF;
-        else if (yq < a_prev) Mleft = (int)PWR_INF;                              // PW:276
+        if (x == 0) Mleft = (src_c < 0 || yq == src_c) ? -gleft : (int)PWR_INF - gleft;
+        else if (yq < a_prev) Mleft = (int)PWR_INF - gleft;                      // PW:276
         else if (needM) Mleft = (int)eMy;
-        else Mleft = gleft + (int)eTx;                                           // PW:285-295
+        else Mleft = (int)eTx;                                                   // PW:285-295
         const int P_in = needP ? (int)ePx : PWR_BIG;
         if (x > 0 && !ran_prev) {
 #pragma unroll
-            for (int i = 0; i < C; ++i) Mprev[i] = (unsigned)(gg[i] + (int)eTx);
+            for (int i = 0; i < C; ++i) Mprev[i] = eTx;
         }
         if ((x >> 4) != gacc) { V4_FLUSH() gacc = x >> 4; }
         V4_ALIGN_ACC(x & 15)
@@ -1986,10 +1998,11 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
             for (int i = 0; i < C; ++i) {
                 accA[i] = (accA[i] << 1) | ((tg[i] >= p) ? 1u : 0u);
                 p = min(p, tg[i]);
-                Mprev[i] = (rel0 + i < 0) ? PWR_INF : (unsigned)(gg[i] + p);
+                Mprev[i] = (unsigned)((rel0 + i < 0) ? ig[i] : p);
             }
         } else {
             // (the DP's last row: only the job's last segment gets here with x == Lf)
+            // (the scores leave the kernel here: Mn is the true M = G + N, as lastM and the test of PW:1386 want it)
             unsigned Mn[C];
             unsigned fa = 0;
 #pragma unroll
@@ -1997,8 +2010,9 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
                 fa |= (tg[i] >= p) ? (1u << i) : 0u;
                 p = min(p, tg[i]);
                 Mn[i] = (rel0 + i < 0) ? PWR_INF : (unsigned)(gg[i] + p);
+                Mprev[i] = (unsigned)((rel0 + i < 0) ? ig[i] : p);
             }
-            const unsigned mrow = needP ? ePy : PWR_INF;
+            const unsigned mrow = needP ? (unsigned)gleft + ePy : PWR_INF;
             const unsigned left0 = (unsigned)__builtin_amdgcn_update_dpp((int)mrow, (int)Mn[C - 1], DPP_WAVE_SHR1, 0xF, 0xF, false);
 #pragma unroll
             for (int i = 0; i < C; ++i) {
@@ -2006,7 +2020,6 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
                 const bool inb = (unsigned)(rel0 + i) < (unsigned)Bx;
                 accA[i] = (accA[i] << 1) | ((((fa >> i) & 1u) || (inb && Mn[i] == lf)) ? 1u : 0u);
                 lastM[wave * MS + lc + i] = inb ? Mn[i] : 0xffffffffu;
-                Mprev[i] = Mn[i];
             }
         }
         nacc = (x & 15) + 1;
