@@ -177,7 +177,7 @@ struct JobBufs {
     uint4 *desc;                   // [njobs][Lmax]   per DP row: {anf | base << 24, flags of waves 0-7, 8-15, 16-23} (4 bits per wave)
     int wpNW, wpMS;                // geometry of the wave pipeline the descriptors are made for
     unsigned *lastM;               // [njobs][NC]     scores of the last DP row (wave-pipeline fill)
-    unsigned long long *gmb;       // [njobs][NW][gstride][2] k_fill_v3: {P_end, tag}, {M_last, tag} per wave and DP row (segments side by side)
+    unsigned long long *gmb;       // [njobs][NW][gstride] k_fill_v3: {P_end, tag} per wave and DP row (segments side by side)
     SegDesc *seg;                  // [njobs][SEG_MAX] plan of the fill (plan_segments, with k_gather_c)
     unsigned *chk;                 // [njobs][SEG_MAX + 1][2][NC] scores of the row before segment s: [0] as s has them after its warm-up, [1] as s - 1 ends
     int seg_align;                 // own parts start at multiples of this (16, 32 or 64)
@@ -1248,17 +1248,18 @@ __global__ __launch_bounds__(NW * 64) void k_fill_v2(DState st, JobBufs jb)   //
 // work-group, so each gets a SIMD to itself (in k_fill_v2 the fifth wave of a work-group shares one with the
 // first, and that pair sets the pace); the grid is (8, NW, jobs / 8) so that the NW work-groups of one DP land
 // on the same XCD and talk through its L2.  What a wave publishes per DP row goes to global memory:
-//   gmb[(w * Lmax + x) * 2 + 0]  {P_end, tag}   the running minimum its right neighbour continues
-//   gmb[(w * Lmax + x) * 2 + 1]  {M_last, tag}  the score of its last column
-// (Ptot, the minimum of the whole row, is the P_end word of the wave that ends the band in that row.)
-// each one aligned 64-bit word, stored and loaded whole (relaxed agent-scope atomics) and self-validating:
+//   gmb[w * gstride + x]  {P_end, tag}   the running minimum its right neighbour continues
+// (Ptot, the minimum of the whole row, is the P_end word of the wave that ends the band in that row; and M_last, the
+// score N = M - G of the wave's last column, which the right neighbour's first column takes as its left score in the next
+// row, is the same number wherever that column lies in the row's band -- DESIGN.md 3.2 --, so it has no word of its own.)
+// One aligned 64-bit word, stored and loaded whole (relaxed agent-scope atomics) and self-validating:
 // tag = launch epoch << 17 | row + 1, so nothing has to be cleared between launches.  There are no rounds and
 // no barriers: a wave simply runs down its rows and waits (bounded by a time-out that flags the job) where a
 // word is missing.  Dependencies only point to the left neighbour, whose own never point back, so this cannot
 // deadlock as long as all NW work-groups are resident -- NW <= 9 per DP, a few dozen DPs per launch, 256 CUs.
 //
 // Every work-group has a second wave, the FETCHER.  It sits on another SIMD of the same CU, polls the left
-// neighbour's published words of the rows [wx - 1, wx + 63) -- wx = the worker's progress -- and copies every
+// neighbour's published word of the rows [wx - 1, wx + 63) -- wx = the worker's progress -- and copies every
 // valid one into an LDS ring; the worker reads the ring exactly as k_fill_v2 reads its mailboxes (one LDS
 // access, waiting in the middle of the row if the word is not there yet).  The worker therefore trails its
 // neighbour by one poll of the fetcher (a few DP rows), and the L2 round trip is never on its critical path.
@@ -1298,7 +1299,7 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
     constexpr int NL = WG1 ? NW : 1;                                      // waves whose tables and rings live in this work-group's LDS
     constexpr int RB = WG1 ? 64 : V4_RB;                                  // ring slots (rows)
     __shared__ __attribute__((aligned(16))) int ldsS1[NL][2][4][MS];
-    __shared__ unsigned long long rP[NL][RB], rM[NL][RB];                // the left neighbour's {P_end, tag}, {M_last, tag}
+    __shared__ unsigned long long rP[NL][RB];                            // the left neighbour's {P_end, tag}
     __shared__ int wprog[NL], wdone;                                     // worker's progress (rows), worker finished
     // virtual job = (job, segment): segment s of job j is slot j * smax + s, so the segments of a job spread over the XCDs
     const int vjob = WG1 ? (int)blockIdx.x : (int)(blockIdx.x + 8 * blockIdx.z), lane = threadIdx.x & 63;
@@ -1323,7 +1324,7 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
     unsigned *const chk_w = jb.chk + (((size_t)job * (SEG_MAX + 1) + sd->s) * 2 + 0) * (size_t)jb.NC;       // [s][0]: this segment after its warm-up
     unsigned *const chk_t = jb.chk + (((size_t)job * (SEG_MAX + 1) + sd->s + 1) * 2 + 1) * (size_t)jb.NC;   // [s + 1][1]: what the next one must match
     const unsigned long long t_clk0 = __builtin_amdgcn_s_memtime(), t_real0 = __builtin_amdgcn_s_memrealtime();
-    for (int i = threadIdx.x; i < NL * RB; i += blockDim.x) { (&rP[0][0])[i] = 0; (&rM[0][0])[i] = 0; }   // (another work-group's words of this launch may lie here)
+    for (int i = threadIdx.x; i < NL * RB; i += blockDim.x) (&rP[0][0])[i] = 0;   // (another work-group's words of this launch may lie here)
     if (threadIdx.x < NL) wprog[threadIdx.x] = 0;
     if (threadIdx.x == 0) wdone = 0;
     __syncthreads();
@@ -1331,12 +1332,12 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
     const int wl = (wave + NW - 1) % NW;
     const unsigned tagbase = jb.tagbase;
     const size_t gstride = (size_t)jb.gstride;
-    unsigned long long *const gmy = jb.gmb + (((size_t)job * NW + wave) * gstride + (size_t)sd->grow0) * 2;
-    const unsigned long long *const gleftw = jb.gmb + (((size_t)job * NW + wl) * gstride + (size_t)sd->grow0) * 2;
+    unsigned long long *const gmy = jb.gmb + ((size_t)job * NW + wave) * gstride + (size_t)sd->grow0;
+    const unsigned long long *const gleftw = jb.gmb + ((size_t)job * NW + wl) * gstride + (size_t)sd->grow0;
     // Ptot(r), the minimum of the whole DP row r (the virtual extension of PW:285-295 is G + Ptot): it is the P_end word of
     // the wave that holds the band's last macro-strip in row r -- read straight from there, on the rare occasions it is needed
-    const unsigned long long *const gjob = jb.gmb + ((size_t)job * NW * gstride + (size_t)sd->grow0) * 2;
-#define PTOT_PTR(AP, BP, R) (gjob + (((size_t)((((AP) + (BP) - 1 - lo) / MS) % NW)) * gstride + (size_t)(R)) * 2)
+    const unsigned long long *const gjob = jb.gmb + (size_t)job * NW * gstride + (size_t)sd->grow0;
+#define PTOT_PTR(AP, BP, R) (gjob + ((size_t)((((AP) + (BP) - 1 - lo) / MS) % NW)) * gstride + (size_t)(R))
     int *const abortf = &m->abort;
 #define GLD(PTR) __hip_atomic_load((PTR), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 #define GST(PTR, VAL, ROW) __hip_atomic_store((PTR), ((unsigned long long)(tagbase | (unsigned)((ROW) + 1)) << 32) | (unsigned)(VAL), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
@@ -1352,19 +1353,13 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
         for (unsigned it = 0;; ++it) {
             if (UNI(LLD(wdone))) break;
             const int wx = UNI(LLD(wprog[lw]));
-            const int r = wx - 1 + lane;                                          // row wx needs words of row wx - 1 too
+            const int r = wx - 1 + lane;                                          // row wx needs the word of row wx - 1 too
             const bool inr = r >= 0 && r < L;
-            unsigned long long p = 0, q = 0;
+            unsigned long long p = 0;
             int ab = 0;
-            if (inr) { p = GLD(gleftw + 2 * (size_t)r); q = GLD(gleftw + 2 * (size_t)r + 1); }
+            if (inr) p = GLD(gleftw + (size_t)r);
             if ((it & 15u) == 15u) ab = GLD(abortf);
-            if (inr) {
-                const unsigned tagr = tagbase | (unsigned)(r + 1);
-                if (TAGOF(p) == tagr && TAGOF(q) == tagr) {
-                    LST(rP[lw][r & (RB - 1)], p);
-                    __hip_atomic_store(&rM[lw][r & (RB - 1)], q, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);   // P before M: M's tag vouches for both
-                }
-            }
+            if (inr && TAGOF(p) == (tagbase | (unsigned)(r + 1))) LST(rP[lw][r & (RB - 1)], p);   // (the word vouches for itself)
             // (no time-out of its own: the worker has one, and its end -- wdone -- or the job's abort flag end this loop)
             if (UNI(ab)) break;
         }
@@ -1542,7 +1537,7 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
                     // The wave's first row on this macro-strip (it has just taken it over, or the band has just reached it).
                     // This is where the pipeline's critical path runs -- the band's last strip can only start when its left
                     // neighbour delivers, and the next one waits for it in turn --, so everything that does not need the
-                    // neighbour's words of row x is done here, before them: the scores the rows above left behind are the
+                    // neighbour's word of row x is done here, before it: the scores the rows above left behind are the
                     // virtual extension G + Ptot(x-1) (PW:285-295), and the score left of the strip is the neighbour's
                     // M_last(x-1), or that extension, or INF (PW:276).  Row x itself then runs like any other row and waits for
                     // P_end(x) only after its scan.
@@ -1557,7 +1552,7 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
                     const unsigned t0 = V3_TICKS();
                     for (unsigned spin = 1;; ++spin) {
                         eT = GLD(PTOT_PTR(a_prev, Bx_prev, x - 1));
-                        eM = LLD(rM[lw][(x - 1) & (RB - 1)]);
+                        eM = LLD(rP[lw][(x - 1) & (RB - 1)]);                        // (M_last(x-1) = P_end(x-1) where needM)
                         if (UNI(TAGOF(eT)) == tagp && (!needM || UNI(TAGOF(eM)) == tagp)) break;
                         if ((spin & 1023u) == 0 && (V3_TICKS() - t0 > V3_TIMEOUT_TICKS || UNI(GLD(abortf)))) { dead = true; break; }
                         __builtin_amdgcn_s_sleep(1);
@@ -1578,12 +1573,12 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
                     ran_prev = 1;
                 } else if ((bMm >> (x & 63)) & 1ull) {
                     const unsigned tagp = tagbase | (unsigned)x;
-                    unsigned long long w_ = LLD(rM[lw][(x - 1) & (RB - 1)]);
+                    unsigned long long w_ = LLD(rP[lw][(x - 1) & (RB - 1)]);
                     if (UNI(TAGOF(w_)) != tagp) {                                   // (bounded by a time-out that flags the job)
                         DG_T0()
                         const unsigned t0 = V3_TICKS();
                         for (unsigned spin = 1;; ++spin) {
-                            w_ = LLD(rM[lw][(x - 1) & (RB - 1)]);
+                            w_ = LLD(rP[lw][(x - 1) & (RB - 1)]);
                             if (UNI(TAGOF(w_)) == tagp) break;
                             if ((spin & 1023u) == 0 && (V3_TICKS() - t0 > V3_TIMEOUT_TICKS || UNI(GLD(abortf)))) { dead = true; break; }
                             __builtin_amdgcn_s_sleep(1);
@@ -1645,9 +1640,9 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
                             if (dead) break;
                         }
                     }
-                    unsigned long long *const gq0 = gmy + 2 * (size_t)g0;
+                    unsigned long long *const gq0 = gmy + (size_t)g0;
                     const unsigned tag_g0 = tagbase | (unsigned)g0;                 // (the rows' tags are this + r + 1)
-                    const unsigned long long *const ringM = &rM[lw][g0 & (RB - 1)], *const ringP = &rP[lw][g0 & (RB - 1)];   // the group's 16 consecutive slots
+                    const unsigned long long *const ringP = &rP[lw][g0 & (RB - 1)];   // the group's 16 consecutive slots
                     // the group's rows in lanes 0..16 of their own registers (lane r: row g0 + r; lane 16: the first row of the next
                     // group, for the look-ahead of the substitution column): every v_readlane below then has a constant lane
                     if (g0 != g_cp) {
@@ -1683,14 +1678,9 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
                             tg[i] = inb ? t3 : FBIG;
                             run = min(run, tg[i]);
                         }
-                        // the neighbour's words of this row, from the ring: M (with the tag) first, the fetcher stores it last
-                        unsigned long long fM = 0;
-                        unsigned fP = 0;
-                        if (CLS != 2) {
-                            fM = LLD(ringM[r]);
-                            __builtin_amdgcn_sched_barrier(0);
-                            fP = __hip_atomic_load((const unsigned *)&ringP[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        }
+                        // the neighbour's word of this row, from the ring: value and tag in one 64-bit read
+                        unsigned long long fP = 0;
+                        if (CLS != 2) fP = LLD(ringP[r]);
                         __builtin_amdgcn_sched_barrier(0);
 #define V4_SCAN_STEP(CTRL, RMASK) { const int t_ = __builtin_amdgcn_update_dpp(PWR_BIG, incl, CTRL, RMASK, 0xF, false); incl = min(incl, t_); }
 #define V4_FENCE() __builtin_amdgcn_sched_barrier(0)
@@ -1708,17 +1698,15 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
                         V4_FENCE(); V4_SCAN_STEP(DPP_ROW_BCAST31, 0xC) V4_FENCE();
 #undef V4_SCAN_STEP
 #undef V4_FENCE
-                        if (bP && __builtin_expect(UNI(TAGOF(fM)) != tagx, 0)) {
+                        if (bP && __builtin_expect(UNI(TAGOF(fP)) != tagx, 0)) {
                             // not there yet: wait for the fetcher to deliver it (bounded by a time-out that flags the job; once it
                             // is flagged the remaining rows of the group run through without waiting)
                             DG_T0()
                             const unsigned t0 = V3_TICKS();
                             for (unsigned spin = 1; !dead; ++spin) {
                                 // (polling the neighbour's global words directly here instead was measured: no faster)
-                                fM = LLD(ringM[r]);
-                                __builtin_amdgcn_sched_barrier(0);
-                                fP = __hip_atomic_load((const unsigned *)&ringP[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                                if (UNI(TAGOF(fM)) == tagx) break;
+                                fP = LLD(ringP[r]);
+                                if (UNI(TAGOF(fP)) == tagx) break;
                                 // time-out: the job is flagged and the loop left after this row -- which is finished with whatever
                                 // is there, nobody will look at the result
                                 if ((spin & 1023u) == 0 && (V3_TICKS() - t0 > V3_TIMEOUT_TICKS || UNI(GLD(abortf)))) { dead = true; break; }
@@ -1726,7 +1714,7 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
                             }
                             DG_ADD(dg_wait_fast)
                         }
-                        const int P_in_v = bP ? (int)fP : PWR_BIG;
+                        const int P_in_v = bP ? (int)(unsigned)fP : PWR_BIG;
                         const int P_end_v = min(P_in_v, incl);
                         const int pq = min(P_in_v, FBIG);
                         int p = min(__builtin_amdgcn_update_dpp(pq, incl, DPP_WAVE_SHR1, 0xF, 0xF, false), pq);
@@ -1737,22 +1725,18 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
                             // N = p: no band guard, so p <= tg[i] <= ig[i] already; behind a guard tg[i] may be FBIG
                             Mprev[i] = (unsigned)(CLS == 0 ? p : min(p, ig[i]));
                         }
-                        mlast_v = (unsigned)fM;
+                        mlast_v = (unsigned)fP;                                     // M_last(x) = P_end(x) wherever the next row reads it
                         if (lane == 63) {
                             if (WG1) {
-                                GST2(gq0 + 2 * r, P_end_v, tagx);
+                                GST2(gq0 + r, P_end_v, tagx);
                                 LST(rP[wr][(g0 + r) & (RB - 1)], ((unsigned long long)tagx << 32) | (unsigned)P_end_v);
-                                LST(rM[wr][(g0 + r) & (RB - 1)], ((unsigned long long)tagx << 32) | (unsigned)Mprev[C - 1]);   // P before M: M's tag vouches for both
                             } else {
-                                // both words in one 16-byte store: each carries its own tag, so it does not matter in which order
-                                // (or in how many pieces) a reader comes to see them
-                                typedef unsigned v4u_ __attribute__((ext_vector_type(4)));
-                                v4u_ w4_; w4_.x = (unsigned)P_end_v; w4_.y = tagx; w4_.z = Mprev[C - 1]; w4_.w = tagx;
-                                // (sc1 as the agent-scope atomic stores have it: the words must be seen by the other work-groups)
-                                // (and the wait states a store of more than 64 bits needs before a VALU may overwrite its data
-                                // registers: the compiler inserts them for its own stores, not behind inline assembly)
+                                typedef unsigned v2u_ __attribute__((ext_vector_type(2)));
+                                v2u_ w2_; w2_.x = (unsigned)P_end_v; w2_.y = tagx;
+                                // (sc1 as the agent-scope atomic stores have it: the word must be seen by the other work-groups; a store
+                                // of 64 bits needs no wait states before a VALU overwrites its data registers)
                                 // (the group's base is wave-uniform: scalar base + the row's byte offset, one move instead of 64-bit address arithmetic)
-                                asm volatile("global_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" :: "v"(16 * r), "v"(w4_), "s"(gq0) : "memory");
+                                asm volatile("global_store_dwordx2 %0, %1, %2 sc1" :: "v"(8 * r), "v"(w2_), "s"(gq0) : "memory");
                             }
                         }
                     };
@@ -1943,10 +1927,12 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
             DG_T0()
             const unsigned t0 = V3_TICKS();
             for (unsigned spin = 1;; ++spin) {
-                const unsigned long long eQ = LLD(rM[lw][x & (RB - 1)]), eP = LLD(rP[lw][x & (RB - 1)]);
-                const unsigned long long eM = LLD(rM[lw][(x - 1) & (RB - 1)]), eT = needT ? GLD(PTOT_PTR(a_prev, Bx_prev, x - 1)) : 0ull;
-                ePx = UNI((unsigned)eP); ePy = UNI((unsigned)eQ); eMy = UNI((unsigned)eM); eTx = UNI((unsigned)eT);
-                const bool ready = (!needP || (UNI(TAGOF(eP)) == tagx && UNI(TAGOF(eQ)) == tagx)) &&
+                // (the neighbour's last column lies in the band of row x where needP, of row x - 1 where needM: its score there is
+                // the P_end word itself)
+                const unsigned long long eP = LLD(rP[lw][x & (RB - 1)]);
+                const unsigned long long eM = LLD(rP[lw][(x - 1) & (RB - 1)]), eT = needT ? GLD(PTOT_PTR(a_prev, Bx_prev, x - 1)) : 0ull;
+                ePx = UNI((unsigned)eP); ePy = ePx; eMy = UNI((unsigned)eM); eTx = UNI((unsigned)eT);
+                const bool ready = (!needP || UNI(TAGOF(eP)) == tagx) &&
                                    (!needM || UNI(TAGOF(eM)) == tagp) && (!needT || UNI(TAGOF(eT)) == tagp);
                 if (ready) break;
                 if ((spin & 1023u) == 0 && (V3_TICKS() - t0 > V3_TIMEOUT_TICKS || UNI(GLD(abortf)))) { dead = true; break; }
@@ -2024,12 +2010,8 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
         }
         nacc = (x & 15) + 1;
         if (lane == 63) {
-            GST(gmy + 2 * (size_t)x, P_end, x);
-            if (WG1) {
-                const unsigned long long tg_ = (unsigned long long)(tagbase | (unsigned)(x + 1)) << 32;
-                LST(rP[wr][x & (RB - 1)], tg_ | (unsigned)P_end);
-                LST(rM[wr][x & (RB - 1)], tg_ | (unsigned)Mprev[C - 1]);
-            } else GST(gmy + 2 * (size_t)x + 1, Mprev[C - 1], x);
+            GST(gmy + (size_t)x, P_end, x);
+            if (WG1) LST(rP[wr][x & (RB - 1)], ((unsigned long long)(tagbase | (unsigned)(x + 1)) << 32) | (unsigned)P_end);
         }
         ran_prev = 1;
         V4_CHK_STORE(x + 1, a, a + Bx)
@@ -4279,7 +4261,7 @@ static int alloc_jobs(pwr_ctx *c, int njobs)
     if ((rc = dmalloc(c, &jb.chk, (size_t)njobs * (SEG_MAX + 1) * 2 * NC))) return rc;
     if (hipMemsetAsync(jb.chk, 0xff, sizeof(unsigned) * (size_t)njobs * (SEG_MAX + 1) * 2 * NC, c->stream) != hipSuccess) return PWR_ERR_DEVICE;
     if (c->fill_mode == 4) {
-        const size_t nmb = (size_t)njobs * c->wp_waves * jb.gstride * 2;
+        const size_t nmb = (size_t)njobs * c->wp_waves * jb.gstride;
         if ((rc = dmalloc(c, &jb.gmb, nmb))) return rc;
         // on the stream the kernels run on (a plain hipMemset is not ordered against it) and waited for
         if (hipMemsetAsync(jb.gmb, 0, nmb * 8, c->stream) != hipSuccess ||
@@ -4570,7 +4552,7 @@ static int launch_fill(pwr_ctx *c, int njobs)
         // one work-group (worker + fetcher wave) per wave of the pipeline; grid.x = 8 keeps the work-groups of a DP
         // on one XCD (work-groups go to the XCDs round-robin by linear id)
         if (++c->fill_epoch >= (1u << 15)) {
-            const size_t nmb = (size_t)c->njobs * c->wp_waves * c->jb.gstride * 2;
+            const size_t nmb = (size_t)c->njobs * c->wp_waves * c->jb.gstride;
             HIPC(hipMemsetAsync(c->jb.gmb, 0, nmb * 8, c->stream));
             c->fill_epoch = 1;
         }

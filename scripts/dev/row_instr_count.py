@@ -1,7 +1,8 @@
 """dev: instructions per DP row of k_fill_v3 in a built libpwr.so:  row_instr_count.py <libpwr.so> [kernel substring]
 
-The straight-line groups of the fast path are 16 copies of one row; every row ends with the 16-byte store of its hand-over
-words (the row marker: `global_store_dwordx4 ... sc1`).  The kernel's code is cut at these stores; a run of at least 12 pieces
+The straight-line groups of the fast path are 16 copies of one row; every row ends with the store of its hand-over word (the
+row marker: `global_store_dwordx2 ... sc1`; the builds that published two words per row end it with
+`global_store_dwordx4 ... sc1`: set MARKER=global_store_dwordx4 in the environment for those).  The kernel's code is cut at these stores; a run of at least 12 pieces
 whose lengths differ by at most one (a wait state more or less) is one straight-line group, and its most frequent length is
 the row's instruction count.  The compiler lays the seven groups out in an order of its own, so they are named by size: the
 three shortest are the warm-up's (no record) and the longest is the one with run-time flags; within the warm-up and within the
@@ -15,6 +16,7 @@ import sys
 import tempfile
 
 OBJDUMP = os.environ.get("LLVM_OBJDUMP", "/opt/rocm/llvm/bin/llvm-objdump")
+MARKER = os.environ.get("MARKER", "global_store_dwordx2")
 
 
 def code_objects(path):
@@ -49,7 +51,7 @@ def main():
     lib = sys.argv[1]
     want = sys.argv[2] if len(sys.argv) > 2 else "_Z9k_fill_v3ILi5ELi4ELb0EEv6DState7JobBufs"
     ins = kernel_lines(lib, want)
-    marks = [i for i, l in enumerate(ins) if l.startswith("global_store_dwordx4") and "sc1" in l]
+    marks = [i for i, l in enumerate(ins) if l.startswith(MARKER) and "sc1" in l]
     gaps = [b - a for a, b in zip(marks, marks[1:])]
     groups, i = [], 0
     while i < len(gaps):
