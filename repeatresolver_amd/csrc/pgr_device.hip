@@ -19,7 +19,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -27,6 +26,9 @@
 #include <cstring>
 #include <vector>
 
+#define PWR_STAGE "pgr"
+#include "dev_util.h"
+#include "four_count_tile.h"
 #include "hyper_tail.h"
 #include "pgr.h"
 #include "pgr_internal.h"
@@ -45,19 +47,13 @@ __device__ __forceinline__ bool better(double z1, int i1, double z2, int i2)
     return z1 > z2 || (z1 == z2 && i1 < i2);
 }
 
-// RR:472-488 Group_PositiveSignificance(G_i, G_a, LC_i, LC_a) from the four counts and the two group sizes.  `floor`: what a
-// value has to reach to matter (greedy, or the 29th of the running list).  The tail is at least its first term, so
-// -log10 pdf(schnitt) bounds the result from above; beyond 97.9 the value is 97.90 + F, which the first term does not bound.
-__device__ __noinline__ double d_gr_significance(const double *__restrict__ lnf, int schnitt, int cov, int gr1, int gr2, int size_i, int size_a, double floor)
+// RR:472-488 Group_PositiveSignificance(G_i, G_a, LC_i, LC_a) from the four counts and the two group sizes: d_tail_z
+// (hyper_tail.h) and this stage's saturated value.  `floor`: what a value has to reach to matter (greedy, or the 29th of
+// the running list).
+__device__ __forceinline__ double d_gr_significance(const double *__restrict__ lnf, int schnitt, int cov, int gr1, int gr2, int size_i, int size_a, double floor)
 {
-    if (gr1 == 0 || gr2 == 0 || schnitt < 1) return 0.0;
-    if (schnitt <= gr2 && schnitt <= gr1 && gr1 - schnitt <= cov - gr2) {
-        const double zb = d_ln_hyper_pdf(lnf, (unsigned)schnitt, (unsigned)gr2, (unsigned)(cov - gr2), (unsigned)gr1) * -0.43429448190325182;
-        if (zb < floor - 1e-6 && zb < 97.9) return 0.0;
-    }
-    double Z = -1.0 * log10(d_hyper_Q(lnf, (unsigned)(schnitt - 1), (unsigned)gr2, (unsigned)(cov - gr2), (unsigned)gr1));   // RR:451-452
-    if (isinf(Z) || Z > 99) Z = 99.0;                                                                                       // RR:453
-    if (isinf(Z) || Z > 98.0) Z = 97.90 + (double)(2 * schnitt) / (double)(size_i + size_a);   // F_beta(., ., 1), RR:432-447: 2s + |i \ a| + |a \ i|
+    double Z = d_tail_z(lnf, schnitt, cov, gr1, gr2, floor);                                   // RR:451-453
+    if (Z > 98.0) Z = 97.90 + (double)(2 * schnitt) / (double)(size_i + size_a);   // F_beta(., ., 1), RR:432-447: 2s + |i \ a| + |a \ i|
     return Z;
 }
 
@@ -76,31 +72,15 @@ __global__ __launch_bounds__(PGR_NT) void k_gr_cliques(int V, int W, int sc, int
     for (int ch = ch0; ch < ch1; ++ch) {
         const int i = ch * PGR_NT + tid;
         const bool have = i < V;
-        const int ii = have ? i / 5 : 0;
         int s[PGR_TA], g1[PGR_TA], g2[PGR_TA], cv[PGR_TA];
 #pragma unroll
         for (int a = 0; a < PGR_TA; ++a) s[a] = g1[a] = g2[a] = cv[a] = 0;
         for (int w0 = 0; w0 < sc; w0 += PGR_WC) {
             __syncthreads();                                           // (everyone is done with the chunk before)
             if (w0 == 0 && tid < PGR_TA) s_cnt[tid] = 0;
-            for (int t = tid; t < PGR_TA * PGR_WC; t += PGR_NT) {
-                const int a = t / PGR_WC, w = w0 + t % PGR_WC, va = s_a[a];
-                const bool ok = va >= 0 && w < sc;
-                sG[a][t % PGR_WC] = ok ? G[(size_t)w * V + va] : 0ull;
-                sL[a][t % PGR_WC] = ok ? LC[(size_t)w * W + va / 5] : 0ull;
-            }
+            tile_stage<PGR_TA, PGR_WC, PGR_NT>(sG, sL, s_a, G, LC, V, W, w0, sc, tid);
             __syncthreads();
-            if (have) {
-                const int wn = min(PGR_WC, sc - w0);
-                for (int w = 0; w < wn; ++w) {
-                    const unsigned long long gi = G[(size_t)(w0 + w) * V + i], li = LC[(size_t)(w0 + w) * W + ii];
-#pragma unroll
-                    for (int a = 0; a < PGR_TA; ++a) {
-                        const unsigned long long ga = sG[a][w], la = sL[a][w];
-                        s[a] += __popcll(gi & ga); g1[a] += __popcll(gi & la); g2[a] += __popcll(ga & li); cv[a] += __popcll(li & la);
-                    }
-                }
-            }
+            if (have) tile_count<PGR_TA, PGR_WC>(sG, sL, G, LC, V, W, w0, sc, i, s, g2, g1, cv);   // g1 = |G_i & LC_a|, g2 = |G_a & LC_i|
         }
         const int si = have ? gsize[i] : 0;
 #pragma unroll
@@ -305,43 +285,11 @@ __global__ __launch_bounds__(256) void k_gr_reldrop(int Vc, int sc, int nk, int 
     }
 }
 
-#define HIPC(call)                                                                     \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                        \
-            fprintf(stderr, "pgr: %s failed: %s\n", #call, hipGetErrorString(e_));    \
-            return PWR_ERR_DEVICE;                                                     \
-        }                                                                              \
-    } while (0)
-
-struct GrBufs {
-    unsigned long long *cg = nullptr, *cc = nullptr;
-    int *Svar = nullptr, *pI = nullptr, *cliques = nullptr, *sizes = nullptr, *cutoffs = nullptr;
-    double *lnf = nullptr, *pZ = nullptr, *drop = nullptr;
-    ~GrBufs()
-    {
-        (void)hipFree(cg); (void)hipFree(cc); (void)hipFree(Svar); (void)hipFree(pI);
-        (void)hipFree(cliques); (void)hipFree(sizes); (void)hipFree(cutoffs); (void)hipFree(lnf); (void)hipFree(pZ); (void)hipFree(drop);
-    }
-};
-
-// the sets of pgr_refine's own window, uploaded from the host reader's
-struct GrSets {
-    unsigned long long *G = nullptr, *LC = nullptr;
-    int *gsize = nullptr;
-    ~GrSets() { (void)hipFree(G); (void)hipFree(LC); (void)hipFree(gsize); }
-};
-
 struct WindowGuard {
     pgr_window w;
     WindowGuard() { memset(&w, 0, sizeof w); }
     ~WindowGuard() { pgr_window_free(&w); }
 };
-
-static double now_ms()
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 extern "C" int pgr_last_timing(double *ms5)
 {
@@ -393,38 +341,38 @@ static int refine_on_device(const unsigned long long *dG, const unsigned long lo
 {
     const size_t V = (size_t)W * 5;
     const int nS = (int)Svar.size();
-    std::vector<double> lnf((size_t)nk + 2);
-    for (int n = 0; n < nk + 2; ++n) lnf[n] = std::lgamma(n + 1.0);
+    const std::vector<double> lnf = hyper_lnf_table(nk);
     const int nch = (int)((V + PGR_NT - 1) / PGR_NT), ntiles = (nS + PGR_TA - 1) / PGR_TA;
     // enough blocks to fill the device when there are few tiles of a, long slices (a better floor) when there are many
     int want = std::max(1, std::min(PGR_MAXSLICES, (2048 + ntiles - 1) / ntiles));
     want = std::min(want, nch);
     const int cps = (nch + want - 1) / want, nslices = (nch + cps - 1) / cps;
-    GrBufs d;
+    typedef unsigned long long u64;
+    DevArena dev;
     const size_t np = (size_t)nS * nslices * PGR_KEEP;
-    if (hipMalloc(&d.Svar, (size_t)nS * 4) != hipSuccess || hipMalloc(&d.lnf, lnf.size() * 8) != hipSuccess || hipMalloc(&d.pZ, np * 8) != hipSuccess ||
-        hipMalloc(&d.pI, np * 4) != hipSuccess || hipMalloc(&d.cliques, (size_t)nS * (PGR_MAXCLIQUE + 1) * 4) != hipSuccess ||
-        hipMalloc(&d.sizes, (size_t)nS * 4) != hipSuccess || hipMalloc(&d.cutoffs, (size_t)nS * 4) != hipSuccess || hipMalloc(&d.drop, (size_t)nS * 8) != hipSuccess ||
-        hipMalloc(&d.cg, (size_t)nS * sc * 8) != hipSuccess || hipMalloc(&d.cc, (size_t)nS * sc * 8) != hipSuccess) return PWR_ERR_NOMEM;
-    HIPC(hipMemcpy(d.Svar, Svar.data(), (size_t)nS * 4, hipMemcpyHostToDevice));
-    HIPC(hipMemcpy(d.lnf, lnf.data(), lnf.size() * 8, hipMemcpyHostToDevice));
-    HIPC(hipMemset(d.cg, 0, (size_t)nS * sc * 8)); HIPC(hipMemset(d.cc, 0, (size_t)nS * sc * 8));
+    const int *d_Svar = dev.put(Svar.data(), nS);
+    const double *d_lnf = dev.put(lnf.data(), lnf.size());
+    double *d_pZ = dev.get<double>(np), *d_drop = dev.get<double>(nS);
+    int *d_pI = dev.get<int>(np), *d_cliques = dev.get<int>((size_t)nS * (PGR_MAXCLIQUE + 1)), *d_sizes = dev.get<int>(nS), *d_cutoffs = dev.get<int>(nS);
+    u64 *d_cg = dev.get<u64>((size_t)nS * sc), *d_cc = dev.get<u64>((size_t)nS * sc);
+    if (!d_Svar || !d_lnf || !d_pZ || !d_drop || !d_pI || !d_cliques || !d_sizes || !d_cutoffs || !d_cg || !d_cc) return dev.err;
+    HIPC(hipMemset(d_cg, 0, (size_t)nS * sc * 8)); HIPC(hipMemset(d_cc, 0, (size_t)nS * sc * 8));
     HIPC(hipDeviceSynchronize());
     const double t1 = now_ms();
-    hipLaunchKernelGGL(k_gr_cliques, dim3(ntiles, nslices), dim3(PGR_NT), 0, 0, (int)V, W, sc, nS, d.Svar, dG, dLC, dgsize, d.lnf, mincov / 4, cutoff,
-                       cps, nslices, d.pZ, d.pI);
+    hipLaunchKernelGGL(k_gr_cliques, dim3(ntiles, nslices), dim3(PGR_NT), 0, 0, (int)V, W, sc, nS, d_Svar, dG, dLC, dgsize, d_lnf, mincov / 4, cutoff,
+                       cps, nslices, d_pZ, d_pI);
     HIPC(hipGetLastError());
     HIPC(hipDeviceSynchronize());
     const double t2 = now_ms();
-    hipLaunchKernelGGL(k_gr_votes, dim3(nS), dim3(256), 0, 0, (int)V, W, sc, nk, nslices, d.Svar, d.pZ, d.pI, dG, dLC, d.cliques, d.sizes, d.cutoffs,
-                       d.drop, d.cg, d.cc);
+    hipLaunchKernelGGL(k_gr_votes, dim3(nS), dim3(256), 0, 0, (int)V, W, sc, nk, nslices, d_Svar, d_pZ, d_pI, dG, dLC, d_cliques, d_sizes, d_cutoffs,
+                       d_drop, d_cg, d_cc);
     HIPC(hipGetLastError());
-    HIPC(hipMemcpy(res->cliques, d.cliques, (size_t)nS * (PGR_MAXCLIQUE + 1) * 4, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(res->sizes, d.sizes, (size_t)nS * 4, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(res->cutoffs, d.cutoffs, (size_t)nS * 4, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(res->drop_off, d.drop, (size_t)nS * 8, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(res->c_groups, d.cg, (size_t)nS * sc * 8, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(res->c_coverage, d.cc, (size_t)nS * sc * 8, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(res->cliques, d_cliques, (size_t)nS * (PGR_MAXCLIQUE + 1) * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(res->sizes, d_sizes, (size_t)nS * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(res->cutoffs, d_cutoffs, (size_t)nS * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(res->drop_off, d_drop, (size_t)nS * 8, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(res->c_groups, d_cg, (size_t)nS * sc * 8, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(res->c_coverage, d_cc, (size_t)nS * sc * 8, hipMemcpyDeviceToHost));
     for (int s = 0; s < nS; ++s)
         if (res->sizes[s] <= 5) res->maxcorrs[Svar[s]] = 0.0;                                    // RR:1686
     ms2[0] = t2 - t1; ms2[1] = now_ms() - t2;
@@ -449,22 +397,17 @@ static int refine(int rows, int width, const unsigned char *text, const double *
     if (hipSetDevice(device) != hipSuccess) return PWR_ERR_DEVICE;
     // word-major copies for the device: the threads of a wave read neighbouring variations of one word
     std::vector<unsigned long long> Gt(V * sc), Lt((size_t)W * sc);
-    std::vector<int> gsize(V);
-    for (size_t v = 0; v < V; ++v) {
-        int g = 0;
-        for (int w = 0; w < sc; ++w) { const unsigned long long x = win.groups[v * sc + w]; Gt[(size_t)w * V + v] = x; g += __builtin_popcountll(x); }
-        gsize[v] = g;
-    }
-    for (int c = 0; c < W; ++c)
-        for (int w = 0; w < sc; ++w) Lt[(size_t)w * W + c] = win.local_coverage[(size_t)c * sc + w];
-    GrSets s;
-    if (hipMalloc(&s.G, V * sc * 8) != hipSuccess || hipMalloc(&s.LC, (size_t)W * sc * 8) != hipSuccess || hipMalloc(&s.gsize, V * 4) != hipSuccess)
-        return PWR_ERR_NOMEM;
-    HIPC(hipMemcpy(s.G, Gt.data(), V * sc * 8, hipMemcpyHostToDevice));
-    HIPC(hipMemcpy(s.LC, Lt.data(), (size_t)W * sc * 8, hipMemcpyHostToDevice));
-    HIPC(hipMemcpy(s.gsize, gsize.data(), V * 4, hipMemcpyHostToDevice));
+    std::vector<int> gsize(V, 0);
+    pgr_word_major(win.groups, sc, nullptr, V, Gt.data());
+    pgr_word_major(win.local_coverage, sc, nullptr, (size_t)W, Lt.data());
+    for (size_t v = 0; v < V; ++v)
+        for (int w = 0; w < sc; ++w) gsize[v] += __builtin_popcountll(win.groups[v * sc + w]);
+    DevArena sets;                                                     // the sets of this call's own window
+    const unsigned long long *dG = sets.put(Gt.data(), Gt.size()), *dLC = sets.put(Lt.data(), Lt.size());
+    const int *dgsize = sets.put(gsize.data(), V);
+    if (!dG || !dLC || !dgsize) return sets.err;
     double ms2[2] = {0, 0};
-    if ((rc = refine_on_device(s.G, s.LC, s.gsize, nk, W, sc, Svar, mincov, cutoff, res, ms2))) return rc;
+    if ((rc = refine_on_device(dG, dLC, dgsize, nk, W, sc, Svar, mincov, cutoff, res, ms2))) return rc;
     const double t3 = now_ms();
     g_ms[0] = t3 - t0; g_ms[2] = ms2[0]; g_ms[3] = ms2[1]; g_ms[1] = g_ms[0] - ms2[0] - ms2[1]; g_ms[4] = (double)nS * (double)(V - 1);
     return PWR_OK;
@@ -477,7 +420,7 @@ extern "C" int pgr_refine(int rows, int width, const unsigned char *text, const 
     memset(result, 0, sizeof *result);
     if (rows <= 0 || width <= 0 || !text || !maxcorrs_full || mincov < 0) return PWR_ERR_ARG;
     if (!(cutoff <= 100.0)) return PWR_ERR_ARG;                        // the trim of RR:1228-1231 needs greedy <= Best_Corrs[0] = 100
-    const int rc = refine(rows, width, text, maxcorrs_full, von, bis, mincov, cutoff, device, result);
+    const int rc = abi_guard([&] { return refine(rows, width, text, maxcorrs_full, von, bis, mincov, cutoff, device, result); });
     if (rc) pgr_free(result);
     return rc;
 }
@@ -490,14 +433,15 @@ int pgr_refine_sets(const pgr_device_sets *sets, const unsigned char *kept, cons
     if (ms2) ms2[0] = ms2[1] = 0;
     if (!sets || !kept || !coverage || !maxcorrs_full || mincov < 0 || !sets->G || !sets->LC || !sets->gsize) return PWR_ERR_ARG;
     if (!(cutoff <= 100.0)) return PWR_ERR_ARG;
-    std::vector<int> Svar;
-    int rc = refine_prepare(sets->rows, sets->kept_rows, sets->width, sets->sc, sets->von, sets->bis, kept, coverage, maxcorrs_full, msa_width,
-                            &cutoff, result, Svar);
     double ms[2] = {0, 0};
-    if (!rc && !Svar.empty()) {
-        if (hipSetDevice(device) != hipSuccess) rc = PWR_ERR_DEVICE;
-        else rc = refine_on_device(sets->G, sets->LC, sets->gsize, sets->kept_rows, sets->width, sets->sc, Svar, mincov, cutoff, result, ms);
-    }
+    const int rc = abi_guard([&] {
+        std::vector<int> Svar;
+        const int rp = refine_prepare(sets->rows, sets->kept_rows, sets->width, sets->sc, sets->von, sets->bis, kept, coverage, maxcorrs_full,
+                                      msa_width, &cutoff, result, Svar);
+        if (rp || Svar.empty()) return rp;
+        if (hipSetDevice(device) != hipSuccess) return PWR_ERR_DEVICE;
+        return refine_on_device(sets->G, sets->LC, sets->gsize, sets->kept_rows, sets->width, sets->sc, Svar, mincov, cutoff, result, ms);
+    });
     if (rc) { pgr_free(result); return rc; }
     if (ms2) { ms2[0] = ms[0]; ms2[1] = ms[1]; }
     return PWR_OK;
@@ -519,13 +463,6 @@ extern "C" void pgr_subdivision_free(pgr_subdivision *o)
     free(o->dropoff_labels); free(o->reldrop_labels); free(o->winner); free(o->winner_cutoff);
     memset(o, 0, sizeof *o);
 }
-
-struct SdBufs {
-    unsigned long long *G = nullptr;
-    int *selcl = nullptr, *selsz = nullptr, *lab = nullptr;
-    unsigned int *best = nullptr;
-    ~SdBufs() { (void)hipFree(G); (void)hipFree(selcl); (void)hipFree(selsz); (void)hipFree(lab); (void)hipFree(best); }
-};
 
 static int subdivide(const pgr_window *win, const pgr_result *r, int mincov, int device, pgr_subdivision *out)
 {
@@ -589,25 +526,21 @@ static int subdivide(const pgr_window *win, const pgr_result *r, int mincov, int
         }
         const size_t Vc = used.size();
         std::vector<unsigned long long> Gt((Vc ? Vc : 1) * sc);
-        for (size_t c = 0; c < Vc; ++c)
-            for (int w = 0; w < sc; ++w) Gt[(size_t)w * Vc + c] = win->groups[(size_t)used[c] * sc + w];
+        pgr_word_major(win->groups, sc, used.data(), Vc, Gt.data());
         std::vector<int> lab((size_t)sc * 64, -1);
         for (int j = 0; j < T; ++j) lab[j] = eidx[U[j]];
-        SdBufs d;
-        if (hipMalloc(&d.G, Gt.size() * 8) != hipSuccess || hipMalloc(&d.selcl, selcl.size() * 4) != hipSuccess ||
-            hipMalloc(&d.selsz, (size_t)nsel * 4) != hipSuccess || hipMalloc(&d.lab, lab.size() * 4) != hipSuccess ||
-            hipMalloc(&d.best, (size_t)E * 4) != hipSuccess) return PWR_ERR_NOMEM;
-        HIPC(hipMemcpy(d.G, Gt.data(), Gt.size() * 8, hipMemcpyHostToDevice));
-        HIPC(hipMemcpy(d.selcl, selcl.data(), selcl.size() * 4, hipMemcpyHostToDevice));
-        HIPC(hipMemcpy(d.selsz, selsz.data(), (size_t)nsel * 4, hipMemcpyHostToDevice));
-        HIPC(hipMemcpy(d.lab, lab.data(), lab.size() * 4, hipMemcpyHostToDevice));
-        HIPC(hipMemset(d.best, 0xff, (size_t)E * 4));
+        DevArena dev;
+        const unsigned long long *d_G = dev.put(Gt.data(), Gt.size());
+        const int *d_selcl = dev.put(selcl.data(), selcl.size()), *d_selsz = dev.put(selsz.data(), nsel), *d_lab = dev.put(lab.data(), lab.size());
+        unsigned int *d_best = dev.get<unsigned int>(E);
+        if (!d_G || !d_selcl || !d_selsz || !d_lab || !d_best) return dev.err;
+        HIPC(hipMemset(d_best, 0xff, (size_t)E * 4));
         HIPC(hipDeviceSynchronize());
         const double t1 = now_ms();
-        hipLaunchKernelGGL(k_gr_reldrop, dim3(nsel), dim3(256), 0, 0, (int)Vc, sc, T, E, mingroup, d.selcl, d.selsz, d.lab, d.G, d.best);
+        hipLaunchKernelGGL(k_gr_reldrop, dim3(nsel), dim3(256), 0, 0, (int)Vc, sc, T, E, mingroup, d_selcl, d_selsz, d_lab, d_G, d_best);
         HIPC(hipGetLastError());
         HIPC(hipDeviceSynchronize());
-        HIPC(hipMemcpy(best.data(), d.best, (size_t)E * 4, hipMemcpyDeviceToHost));
+        HIPC(hipMemcpy(best.data(), d_best, (size_t)E * 4, hipMemcpyDeviceToHost));
         g_sd_ms[2] = t1 - t0; g_sd_ms[3] = now_ms() - t1;
     }
     const double t2 = now_ms();
@@ -642,7 +575,7 @@ extern "C" int pgr_subdivide(const pgr_window *win, const pgr_result *refined, i
     if (win->rows != refined->rows || win->kept_rows != refined->kept_rows || win->sc != refined->sc || win->width != refined->width) return PWR_ERR_ARG;
     if (win->rows < 0 || win->kept_rows < 0 || win->kept_rows > win->rows || win->width <= 0 || win->sc != win->kept_rows / 64 + 1 || refined->nsig < 0) return PWR_ERR_ARG;
     if (refined->nsig > 0 && (!refined->significant || !refined->maxcorrs || !refined->sizes || !refined->cliques || !refined->drop_off || !refined->c_groups)) return PWR_ERR_ARG;
-    const int rc = subdivide(win, refined, mincov, device, out);
+    const int rc = abi_guard([&] { return subdivide(win, refined, mincov, device, out); });
     if (rc) pgr_subdivision_free(out);
     return rc;
 }

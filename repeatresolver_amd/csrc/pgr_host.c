@@ -3,6 +3,8 @@
  * drop-off subdivisions (RR:568-585, RR:1823-1865, RR:3180-3271); at the end the reassignment chain of Kmeans (RR:2726-2755). */
 #define _POSIX_C_SOURCE 200809L
 #include "pgr.h"
+#include "base_code.h"
+#include "pgr_internal.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -10,15 +12,11 @@
 #include <string.h>
 #include <time.h>
 
-static int code_of(unsigned char ch)
+void pgr_word_major(const unsigned long long *sets, int sc, const int *pick, size_t n, unsigned long long *out)
 {
-    switch (ch) {                                                                  /* RR:336-359 */
-    case 'a': case 'A': return 0;
-    case 'c': case 'C': return 1;
-    case 'g': case 'G': return 2;
-    case 't': case 'T': return 3;
-    case '-': case '_': return 4;
-    default: return 5;
+    for (size_t c = 0; c < n; c++) {
+        const unsigned long long *set = sets + (pick ? (size_t)pick[c] : c) * sc;
+        for (int w = 0; w < sc; w++) out[(size_t)w * n + c] = set[w];
     }
 }
 
@@ -60,7 +58,7 @@ int pgr_read_window(int rows, int width, const unsigned char *text, int von, int
         const unsigned char *line = text + (size_t)r * width + von;
         const unsigned long long bit = 1ull << (j % 64);
         for (int i = 0; i < w; i++) {
-            const int k = code_of(line[i]);
+            const int k = base_code(line[i]);                                  /* RR:336-359 */
             if (k < 5) {                                                           /* RR:402-420 */
                 win->groups[((size_t)i * 5 + k) * sc + j / 64] |= bit;
                 win->local_coverage[(size_t)i * sc + j / 64] |= bit;

@@ -1,4 +1,4 @@
-/* pgr_internal.h -- what pgr_device.hip and pgr_win_device.hip share inside libpwr.so; not part of the C ABI. */
+/* pgr_internal.h -- what pgr_host.c and the pgr_*_device.hip files share inside libpwr.so; not part of the C ABI. */
 #ifndef PGR_INTERNAL_H
 #define PGR_INTERNAL_H
 
@@ -18,4 +18,13 @@ typedef struct {
 __attribute__((visibility("hidden"))) int pgr_refine_sets(const pgr_device_sets *sets, const unsigned char *kept, const int *coverage,
                                                           const double *maxcorrs_full, int msa_width, int mincov, double cutoff, int device,
                                                           pgr_result *result, double *ms2);
+
+/* Set-major to word-major, as the kernels read a window's sets: out[w * n + c] = sets[pick[c] * sc + w] for the n sets
+ * pick[0 .. n) of sc words each (pick = NULL: all of them, pick[c] = c).  out[sc * n].  It is a transposition, so the way
+ * back is the same call with the two extents exchanged: pgr_word_major(word_major, n, NULL, sc, set_major). */
+#ifdef __cplusplus
+extern "C"
+#endif
+__attribute__((visibility("hidden"))) void pgr_word_major(const unsigned long long *sets, int sc, const int *pick, size_t n,
+                                                          unsigned long long *out);
 #endif

@@ -24,17 +24,18 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <new>
 #include <vector>
 
+#define PWR_STAGE "pgr"
+#include "dev_util.h"
 #include "hyper_tail.h"
 #include "pgr.h"
+#include "pgr_internal.h"
 
 #define PKM_NT 256                  // threads per block
 #define PKM_TB 16                   // partners per tile of k_km_pairs
@@ -230,34 +231,7 @@ __global__ __launch_bounds__(PKM_NT) void k_km_assign(const KmPart *__restrict__
     if (have) cluster[p.roff + i] = best_j;                            // RR:2721
 }
 
-#define HIPC(call)                                                                     \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                        \
-            fprintf(stderr, "pgr: %s failed: %s\n", #call, hipGetErrorString(e_));    \
-            return PWR_ERR_DEVICE;                                                     \
-        }                                                                              \
-    } while (0)
-
 namespace {
-// device allocations of one call, released together
-struct KmBufs {
-    std::vector<void *> all;
-    template <class T> T *get(size_t n)
-    {
-        void *p = nullptr;
-        if (hipMalloc(&p, (n ? n : 1) * sizeof(T)) != hipSuccess) return nullptr;
-        all.push_back(p);
-        return (T *)p;
-    }
-    ~KmBufs() { for (void *p : all) (void)hipFree(p); }
-};
-
-double km_now_ms()
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 template <class T> T *km_copy(const std::vector<T> &v)
 {
     T *p = (T *)malloc(sizeof(T) * (v.size() ? v.size() : 1));
@@ -283,7 +257,7 @@ extern "C" void pgr_kmeans_free(pgr_kmeans *o)
 
 static int kmeans(const pgr_window *win, const pgr_result *r, const int *labels_rows, int mincov, int device, bool want_pairs, pgr_kmeans *out)
 {
-    const double t0 = km_now_ms();
+    const double t0 = now_ms();
     const int rows = win->rows, T = win->kept_rows, sc = win->sc, mingroup = mincov / 2;       // RR:4028
     const size_t V = (size_t)win->width * 5;
     for (int i = 0; i < 6; ++i) g_km_ms[i] = 0;
@@ -322,25 +296,22 @@ static int kmeans(const pgr_window *win, const pgr_result *r, const int *labels_
     long long npairs = 0;
     if (E > 0) {
         if (hipSetDevice(device) != hipSuccess) return PWR_ERR_DEVICE;
-        KmBufs d;
+        DevArena d;
         // ---- Relative_Vars: the variations over the cutoff (RR:2430-2434), word-major as in pgr_refine ----
         std::vector<int> cand;
         for (size_t v = 0; v < V; ++v)
             if (r->maxcorrs[v] > r->cutoff) cand.push_back((int)v);
         const int nC = (int)cand.size();
         std::vector<u64> Gc((size_t)(nC ? nC : 1) * sc), Ue((size_t)E * sc, 0ull);
-        for (int c = 0; c < nC; ++c)
-            for (int w = 0; w < sc; ++w) Gc[(size_t)w * nC + c] = win->groups[(size_t)cand[c] * sc + w];
+        pgr_word_major(win->groups, sc, cand.data(), (size_t)nC, Gc.data());
         for (int e = 0; e < E; ++e)
             for (int q = roff[e]; q < roff[e + 1]; ++q) Ue[(size_t)e * sc + prow[q] / 64] |= 1ull << (prow[q] % 64);   // RR:2438
         std::vector<int> poff((size_t)E + 1, 0), pcol, pvar, pgr_, pcov(E);
         std::vector<double> maxZ;
         if (nC > 0) {
-            u64 *dG = d.get<u64>(Gc.size()), *dU = d.get<u64>(Ue.size());
+            const u64 *dG = d.put(Gc.data(), Gc.size()), *dU = d.put(Ue.data(), Ue.size());
             int *dcnt = d.get<int>((size_t)E * nC);
-            if (!dG || !dU || !dcnt) return PWR_ERR_NOMEM;
-            HIPC(hipMemcpy(dG, Gc.data(), Gc.size() * 8, hipMemcpyHostToDevice));
-            HIPC(hipMemcpy(dU, Ue.data(), Ue.size() * 8, hipMemcpyHostToDevice));
+            if (!dG || !dU || !dcnt) return d.err;
             hipLaunchKernelGGL(k_km_counts, dim3((nC + PKM_NT - 1) / PKM_NT, E), dim3(PKM_NT), 0, 0, nC, sc, dG, dU, dcnt);
             HIPC(hipGetLastError());
             std::vector<int> cnt((size_t)E * nC);
@@ -363,37 +334,31 @@ static int kmeans(const pgr_window *win, const pgr_result *r, const int *labels_
             }
             if ((nmax + PKM_ZB - 1) / PKM_ZB > 65535) return PWR_ERR_RANGE;          // the partners are the grid's z dimension
             if (want_pairs && (dtotal > PKM_MAX_DEBUG || (u64)npairs > PKM_MAX_DEBUG)) return PWR_ERR_RANGE;
-            g_km_ms[1] = km_now_ms() - t0;
-            const double t1 = km_now_ms();
+            g_km_ms[1] = now_ms() - t0;
+            const double t1 = now_ms();
             const size_t np = pcol.size();
             maxZ.assign(np, 0.0);
             if (nmax > 0) {
-                std::vector<double> lnf((size_t)T + 2);
-                for (int n = 0; n < T + 2; ++n) lnf[n] = std::lgamma(n + 1.0);
-                int *dpoff = d.get<int>(poff.size()), *dpcol = d.get<int>(np), *dpvar = d.get<int>(np), *dpgr = d.get<int>(np), *dpcov = d.get<int>(E);
-                double *dlnf = d.get<double>(lnf.size()), *dmaxZ = d.get<double>(np), *ddbg = nullptr;
-                u64 *ddoff = d.get<u64>(E);
-                if (!dpoff || !dpcol || !dpvar || !dpgr || !dpcov || !dlnf || !dmaxZ || !ddoff) return PWR_ERR_NOMEM;
+                const std::vector<double> lnf = hyper_lnf_table(T);
+                const int *dpoff = d.put(poff.data(), poff.size()), *dpcol = d.put(pcol.data(), np), *dpvar = d.put(pvar.data(), np),
+                          *dpgr = d.put(pgr_.data(), np), *dpcov = d.put(pcov.data(), E);
+                const double *dlnf = d.put(lnf.data(), lnf.size());
+                const u64 *ddoff = d.put(doff.data(), E);
+                double *dmaxZ = d.get<double>(np), *ddbg = nullptr;
+                if (!dpoff || !dpcol || !dpvar || !dpgr || !dpcov || !dlnf || !dmaxZ || !ddoff) return d.err;
                 if (want_pairs) {
                     if (!(ddbg = d.get<double>((size_t)dtotal))) return PWR_ERR_NOMEM;
                     HIPC(hipMemset(ddbg, 0, (size_t)(dtotal ? dtotal : 1) * 8));
                 }
-                HIPC(hipMemcpy(dpoff, poff.data(), poff.size() * 4, hipMemcpyHostToDevice));
-                HIPC(hipMemcpy(dpcol, pcol.data(), np * 4, hipMemcpyHostToDevice));
-                HIPC(hipMemcpy(dpvar, pvar.data(), np * 4, hipMemcpyHostToDevice));
-                HIPC(hipMemcpy(dpgr, pgr_.data(), np * 4, hipMemcpyHostToDevice));
-                HIPC(hipMemcpy(dpcov, pcov.data(), (size_t)E * 4, hipMemcpyHostToDevice));
-                HIPC(hipMemcpy(dlnf, lnf.data(), lnf.size() * 8, hipMemcpyHostToDevice));
-                HIPC(hipMemcpy(ddoff, doff.data(), (size_t)E * 8, hipMemcpyHostToDevice));
                 HIPC(hipMemset(dmaxZ, 0, (np ? np : 1) * 8));
                 HIPC(hipDeviceSynchronize());
-                const double t1b = km_now_ms();
+                const double t1b = now_ms();
                 g_km_ms[1] += t1b - t1;
                 hipLaunchKernelGGL(k_km_pairs, dim3((nmax + PKM_NT - 1) / PKM_NT, E, (nmax + PKM_ZB - 1) / PKM_ZB), dim3(PKM_NT), 0, 0, nC, sc, dpoff, dpcol, dpvar, dpgr, dpcov, dG, dU,
                                    dlnf, dmaxZ, ddoff, ddbg);
                 HIPC(hipGetLastError());
                 HIPC(hipDeviceSynchronize());
-                g_km_ms[2] = km_now_ms() - t1b;
+                g_km_ms[2] = now_ms() - t1b;
                 HIPC(hipMemcpy(maxZ.data(), dmaxZ, np * 8, hipMemcpyDeviceToHost));
                 if (want_pairs && dtotal > 0) {
                     std::vector<double> dbg((size_t)dtotal);
@@ -417,7 +382,7 @@ static int kmeans(const pgr_window *win, const pgr_result *r, const int *labels_
             voff[e + 1] = (int)vars.size();
         }
         // ---- Kmeans: VarSigs (RR:2633-2640), word-major per part ----
-        const double t2 = km_now_ms();
+        const double t2 = now_ms();
         const bool chain = mingroup > 2;                               // RR:2727: min = 2 .. mingroup - 1
         std::vector<KmPart> kp(E);
         u64 words = 0, scores = 0;
@@ -442,13 +407,12 @@ static int kmeans(const pgr_window *win, const pgr_result *r, const int *labels_
                     dst[i] |= ((g[row / 64] >> (row % 64)) & 1ull) << (jj % 64);
                 }
             }
-        KmPart *dkp = d.get<KmPart>(E);
-        u64 *dVS = d.get<u64>((size_t)words), *dCT = d.get<u64>((size_t)words);
+        const KmPart *dkp = d.put(kp.data(), E);
+        const u64 *dVS = d.put(VS.data(), (size_t)words);
+        u64 *dCT = d.get<u64>((size_t)words);
         int *dcl = d.get<int>((size_t)roff[E]);
         unsigned short *dS = chain ? d.get<unsigned short>((size_t)scores) : nullptr;
-        if (!dkp || !dVS || !dCT || !dcl || (chain && !dS)) return PWR_ERR_NOMEM;
-        HIPC(hipMemcpy(dkp, kp.data(), sizeof(KmPart) * E, hipMemcpyHostToDevice));
-        HIPC(hipMemcpy(dVS, VS.data(), (size_t)words * 8, hipMemcpyHostToDevice));
+        if (!dkp || !dVS || !dCT || !dcl || (chain && !dS)) return d.err;
         const dim3 grid((amax + PKM_NT - 1) / PKM_NT, E);
         hipLaunchKernelGGL(k_km_centroids, grid, dim3(PKM_NT), 0, 0, dkp, dVS, dCT);
         HIPC(hipGetLastError());
@@ -460,7 +424,7 @@ static int kmeans(const pgr_window *win, const pgr_result *r, const int *labels_
             S.resize((size_t)scores);
             HIPC(hipMemcpy(S.data(), dS, (size_t)scores * 2, hipMemcpyDeviceToHost));
         }
-        const double t3 = km_now_ms();
+        const double t3 = now_ms();
         g_km_ms[3] = t3 - t2;
         after = before;
         int max_u = number > 0 ? number - 1 : 0;                       // RR:2813-2814
@@ -479,7 +443,7 @@ static int kmeans(const pgr_window *win, const pgr_result *r, const int *labels_
                 max_u = std::max(max_u, base + cl[i]);
             }
         }
-        g_km_ms[4] = km_now_ms() - t3;
+        g_km_ms[4] = now_ms() - t3;
     }
     const int parts = pgr_compress_labels(T, U.data());                // RR:3398
     if (parts < 0) return parts;
@@ -497,7 +461,7 @@ static int kmeans(const pgr_window *win, const pgr_result *r, const int *labels_
         !out->var_offset || !out->vars || !out->pair_part || !out->pair_i || !out->pair_j || !out->pair_z) return PWR_ERR_NOMEM;
     out->pairs = npairs;
     out->debug_pairs = (long long)dpz.size();
-    g_km_ms[0] = km_now_ms() - t0; g_km_ms[5] = (double)npairs;
+    g_km_ms[0] = now_ms() - t0; g_km_ms[5] = (double)npairs;
     return PWR_OK;
 }
 
@@ -509,12 +473,7 @@ static int kmeans_checked(const pgr_window *win, const pgr_result *refined, cons
     if (!win || !refined || !labels_rows || mincov < 0 || !win->kept || !win->groups || !refined->maxcorrs) return PWR_ERR_ARG;
     if (win->rows != refined->rows || win->kept_rows != refined->kept_rows || win->sc != refined->sc || win->width != refined->width) return PWR_ERR_ARG;
     if (win->rows < 0 || win->kept_rows < 0 || win->kept_rows > win->rows || win->width <= 0 || win->sc != win->kept_rows / 64 + 1) return PWR_ERR_ARG;
-    int rc;
-    try {
-        rc = kmeans(win, refined, labels_rows, mincov, device, want_pairs, out);
-    } catch (const std::bad_alloc &) {                                 // a host vector: no exception leaves the C ABI
-        rc = PWR_ERR_NOMEM;
-    }
+    const int rc = abi_guard([&] { return kmeans(win, refined, labels_rows, mincov, device, want_pairs, out); });
     if (rc) pgr_kmeans_free(out);
     return rc;
 }

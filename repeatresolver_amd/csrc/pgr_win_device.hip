@@ -13,23 +13,16 @@
 // Every index into the text is 64-bit: rows * width exceeds 2^31 at the size of a real data set.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
+#define PWR_STAGE "pgr"
+#include "base_code.h"
+#include "dev_util.h"
 #include "pgr.h"
 #include "pgr_internal.h"
-
-#define HIPC(call)                                                                     \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                        \
-            fprintf(stderr, "pgr: %s failed: %s\n", #call, hipGetErrorString(e_));    \
-            return PWR_ERR_DEVICE;                                                     \
-        }                                                                              \
-    } while (0)
 
 struct pgr_msa {
     int rows, width, device;
@@ -37,23 +30,6 @@ struct pgr_msa {
 };
 
 static double g_rs_ms[7] = {0, 0, 0, 0, 0, 0, 0};
-
-static double now_ms()
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-__device__ __forceinline__ int d_code_of(unsigned char ch)
-{
-    switch (ch) {                                                      // RR:336-359
-    case 'a': case 'A': return 0;
-    case 'c': case 'C': return 1;
-    case 'g': case 'G': return 2;
-    case 't': case 'T': return 3;
-    case '-': case '_': return 4;
-    default: return 5;
-    }
-}
 
 __global__ __launch_bounds__(256) void k_win_kept(int rows, long long width, int von, int bis, const unsigned char *__restrict__ text,
                                                   unsigned char *__restrict__ flag)
@@ -74,7 +50,7 @@ __global__ __launch_bounds__(256) void k_win_bits(int nk, int W, long long width
     unsigned long long g[5] = {0, 0, 0, 0, 0};
     const int n = min(64, nk - w * 64);                                // (the last word may hold no row at all: sc = nk / 64 + 1)
     for (int r = 0; r < n; ++r) {
-        const int k = d_code_of(text[(long long)list[w * 64 + r] * width + von + c]);
+        const int k = base_code(text[(long long)list[w * 64 + r] * width + von + c]);
 #pragma unroll
         for (int q = 0; q < 5; ++q) g[q] |= (unsigned long long)(k == q) << r;
     }
@@ -97,7 +73,7 @@ struct DevWindow {
     int *gsize = nullptr, *cover = nullptr, *list = nullptr;
     unsigned char *flag = nullptr;
     std::vector<unsigned char> kept;
-    ~DevWindow() { (void)hipFree(G); (void)hipFree(LC); (void)hipFree(gsize); (void)hipFree(cover); (void)hipFree(list); (void)hipFree(flag); }
+    DevArena mem;                                                      // owns the pointers above
 };
 
 // Einlesen on the device: the argument checks and their order are pgr_read_window's
@@ -110,7 +86,7 @@ static int read_on_device(const pgr_msa *h, int von, int bis, DevWindow &d)
     const int W = bis + 1 - von;                                                   // RR:374
     d.rows = rows; d.von = von; d.bis = bis; d.width = W;
     if (hipSetDevice(h->device) != hipSuccess) return PWR_ERR_DEVICE;
-    if (hipMalloc(&d.flag, (size_t)rows) != hipSuccess) return PWR_ERR_NOMEM;
+    if (!(d.flag = d.mem.get<unsigned char>(rows))) return PWR_ERR_NOMEM;
     hipLaunchKernelGGL(k_win_kept, dim3((rows + 255) / 256), dim3(256), 0, 0, rows, (long long)width, von, bis, h->text, d.flag);
     HIPC(hipGetLastError());
     d.kept.resize((size_t)rows);
@@ -120,9 +96,9 @@ static int read_on_device(const pgr_msa *h, int von, int bis, DevWindow &d)
     const int nk = (int)list.size(), sc = nk / 64 + 1;                             // RR:375
     d.kept_rows = nk; d.sc = sc;
     const size_t V = (size_t)W * 5;
-    if (hipMalloc(&d.G, V * sc * 8) != hipSuccess || hipMalloc(&d.LC, (size_t)W * sc * 8) != hipSuccess || hipMalloc(&d.gsize, V * 4) != hipSuccess ||
-        hipMalloc(&d.cover, (size_t)W * 4) != hipSuccess || hipMalloc(&d.list, (size_t)(nk ? nk : 1) * 4) != hipSuccess) return PWR_ERR_NOMEM;
-    if (nk) HIPC(hipMemcpy(d.list, list.data(), (size_t)nk * 4, hipMemcpyHostToDevice));
+    d.G = d.mem.get<unsigned long long>(V * sc); d.LC = d.mem.get<unsigned long long>((size_t)W * sc);
+    d.gsize = d.mem.get<int>(V); d.cover = d.mem.get<int>(W); d.list = d.mem.put(list.data(), nk);
+    if (!d.G || !d.LC || !d.gsize || !d.cover || !d.list) return d.mem.err;
     HIPC(hipMemset(d.gsize, 0, V * 4));
     HIPC(hipMemset(d.cover, 0, (size_t)W * 4));
     hipLaunchKernelGGL(k_win_bits, dim3((W + 255) / 256, sc), dim3(256), 0, 0, nk, W, (long long)width, von, h->text, d.list, d.G, d.LC, d.gsize,
@@ -152,11 +128,9 @@ static int download(const DevWindow &d, pgr_window *win)
     }
     std::vector<unsigned long long> t(V * sc);
     HIPC(hipMemcpy(t.data(), d.G, V * sc * 8, hipMemcpyDeviceToHost));
-    for (int w = 0; w < sc; ++w)
-        for (size_t v = 0; v < V; ++v) win->groups[v * sc + w] = t[(size_t)w * V + v];
+    pgr_word_major(t.data(), (int)V, nullptr, (size_t)sc, win->groups);                // (the way back: the extents exchanged)
     HIPC(hipMemcpy(t.data(), d.LC, (size_t)W * sc * 8, hipMemcpyDeviceToHost));
-    for (int w = 0; w < sc; ++w)
-        for (int c = 0; c < W; ++c) win->local_coverage[(size_t)c * sc + w] = t[(size_t)w * W + c];
+    pgr_word_major(t.data(), W, nullptr, (size_t)sc, win->local_coverage);
     return PWR_OK;
 }
 
@@ -191,9 +165,11 @@ extern "C" int pgr_msa_window(pgr_msa *h, int von, int bis, pgr_window *win)
     if (!win) return PWR_ERR_ARG;
     memset(win, 0, sizeof *win);
     if (!h) return PWR_ERR_ARG;
-    DevWindow d;
-    int rc = read_on_device(h, von, bis, d);
-    if (!rc) rc = download(d, win);
+    const int rc = abi_guard([&] {
+        DevWindow d;
+        const int rd = read_on_device(h, von, bis, d);
+        return rd ? rd : download(d, win);
+    });
     if (rc) pgr_window_free(win);
     return rc;
 }
@@ -266,7 +242,7 @@ extern "C" int pgr_msa_resolve(pgr_msa *h, const double *maxcorrs_full, int nsit
     out->windows = (pgr_resolved_window *)calloc((size_t)(nsites - 1), sizeof(pgr_resolved_window));
     if (!out->windows) { pgr_resolution_free(out); return PWR_ERR_NOMEM; }
     for (int p = 0; p + 1 < nsites; ++p) {
-        const int rc = resolve_window(h, maxcorrs_full, sites[p], sites[p + 1], mincov, cutoff, out->windows + p);
+        const int rc = abi_guard([&] { return resolve_window(h, maxcorrs_full, sites[p], sites[p + 1], mincov, cutoff, out->windows + p); });
         if (rc) { pgr_resolution_free(out); return rc; }
     }
     g_rs_ms[1] = now_ms() - t0;

@@ -30,6 +30,8 @@
 #include <numeric>
 #include <vector>
 
+#define PWR_STAGE "pia"
+#include "dev_util.h"
 #include "pia.h"
 
 #define IA_MAXWPL 35                // 70 000 template bases / (64 lanes x 32 bits)
@@ -211,15 +213,6 @@ struct pia_ctx {
                                                   // allocates come at once, every further GB takes 30 ms)
 };
 
-#define HIPC(call)                                                                     \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                        \
-            fprintf(stderr, "pia: %s failed: %s\n", #call, hipGetErrorString(e_));    \
-            return PWR_ERR_DEVICE;                                                     \
-        }                                                                              \
-    } while (0)
-
 // the kernels take a base's code from two bits of its character ((c >> 1) & 3: a c g t, either case): anything else would
 // silently alias one of the four, so it is refused at the boundary
 static inline bool ia_is_base(char ch)
@@ -227,22 +220,21 @@ static inline bool ia_is_base(char ch)
     switch (ch) { case 'a': case 'c': case 'g': case 't': case 'A': case 'C': case 'G': case 'T': return true; default: return false; }
 }
 
-extern "C" int pia_create(pia_ctx **out, const char *templ, int templ_len, int device)
+static int create(pia_ctx **out, const char *templ, int templ_len, int device)
 {
     if (!out || !templ || templ_len < 0) return PWR_ERR_ARG;
     if (templ_len > PIA_MAX_LINE) return PWR_ERR_RANGE;                              // IA:214 Template[70000]
     for (int y = 0; y < templ_len; ++y) if (!ia_is_base(templ[y])) return PWR_ERR_INPUT;     // (the reference's reader leaves nothing else, IA:190-209)
-    pia_ctx *c = new (std::nothrow) pia_ctx();
-    if (!c) return PWR_ERR_NOMEM;
-    c->device = device; c->L2 = templ_len;
-    c->WPL = std::max(1, (templ_len + 2047) / 2048);
-    const int NW = 64 * c->WPL;
-    std::vector<uint32_t> planes(2 * (size_t)NW, 0u);
+    const int WPL = std::max(1, (templ_len + 2047) / 2048), NW = 64 * WPL;
+    std::vector<uint32_t> planes(2 * (size_t)NW, 0u);                                // (before the context: nothing below throws)
     for (int y = 0; y < templ_len; ++y) {
         const int code = (templ[y] >> 1) & 3;
         if (code & 1) planes[y >> 5] |= 1u << (y & 31);
         if (code & 2) planes[NW + (y >> 5)] |= 1u << (y & 31);
     }
+    pia_ctx *c = new (std::nothrow) pia_ctx();
+    if (!c) return PWR_ERR_NOMEM;
+    c->device = device; c->L2 = templ_len; c->WPL = WPL;
     if (hipSetDevice(device) != hipSuccess) { delete c; return PWR_ERR_DEVICE; }
     if (hipMalloc(&c->d_planes, planes.size() * 4) != hipSuccess) { delete c; return PWR_ERR_NOMEM; }
     if (hipMemcpy(c->d_planes, planes.data(), planes.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
@@ -255,6 +247,11 @@ extern "C" int pia_create(pia_ctx **out, const char *templ, int templ_len, int d
     c->stream = c->streams[0];
     *out = c;
     return PWR_OK;
+}
+
+extern "C" int pia_create(pia_ctx **out, const char *templ, int templ_len, int device)
+{
+    return abi_guard([&] { return create(out, templ, templ_len, device); });
 }
 
 extern "C" void pia_destroy(pia_ctx *c)
@@ -289,13 +286,6 @@ extern "C" int pia_get_timing(pia_ctx *c, double *ms6)
     return PWR_OK;
 }
 
-static double now_ms()
-{
-    timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
-}
-
 template <int WPL>
 static void launch_bits(pia_ctx *c, bool store, int n, const char *d_bases, IaRead *d_reads, const int *d_order, uint2 *d_codes, int *d_align, hipStream_t st)
 {
@@ -309,18 +299,18 @@ static void launch_bits(pia_ctx *c, bool store, int n, const char *d_bases, IaRe
 
 struct DevBufs {                    // freed on every way out of pia_align
     char *bases = nullptr; IaRead *reads = nullptr; int *order = nullptr; int *align = nullptr;
+    DevArena mem;                   // owns the four above
     hipEvent_t e0 = nullptr, e1 = nullptr;
     std::vector<hipEvent_t> ev;
     ~DevBufs()
     {
-        (void)hipFree(bases); (void)hipFree(reads); (void)hipFree(order); (void)hipFree(align);
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
         if (e0) (void)hipEventDestroy(e0);
         if (e1) (void)hipEventDestroy(e1);
     }
 };
 
-extern "C" int pia_align(pia_ctx *c, int nreads, const char *bases, const long long *off, int *align, int *dist)
+static int align_reads(pia_ctx *c, int nreads, const char *bases, const long long *off, int *align, int *dist)
 {
     if (!c || nreads < 0 || !off || (nreads && (!bases || !align || !dist))) return PWR_ERR_ARG;
     if (nreads == 0) return PWR_OK;
@@ -350,8 +340,8 @@ extern "C" int pia_align(pia_ctx *c, int nreads, const char *bases, const long l
     }
     DevBufs d;
     HIPC(hipEventCreate(&d.e0)); HIPC(hipEventCreate(&d.e1));
-    if (hipMalloc(&d.bases, std::max<long long>(nb, 1)) != hipSuccess || hipMalloc(&d.reads, sizeof(IaRead) * nreads) != hipSuccess ||
-        hipMalloc(&d.order, sizeof(int) * nreads) != hipSuccess || hipMalloc(&d.align, sizeof(int) * std::max<long long>(nb, 1)) != hipSuccess) return PWR_ERR_NOMEM;
+    d.bases = d.mem.get<char>(nb); d.reads = d.mem.get<IaRead>(nreads); d.order = d.mem.get<int>(nreads); d.align = d.mem.get<int>(nb);
+    if (!d.bases || !d.reads || !d.order || !d.align) return PWR_ERR_NOMEM;
     if (nb) HIPC(hipMemcpyAsync(d.bases, bases + b0, nb, hipMemcpyHostToDevice, c->stream));
     HIPC(hipMemcpyAsync(d.reads, hr.data(), sizeof(IaRead) * nreads, hipMemcpyHostToDevice, c->stream));
     HIPC(hipMemcpyAsync(d.order, order.data(), sizeof(int) * nreads, hipMemcpyHostToDevice, c->stream));
@@ -436,4 +426,9 @@ extern "C" int pia_align(pia_ctx *c, int nreads, const char *bases, const long l
     c->t_ms[5] = now_ms() - t_dl;
     c->t_ms[0] = now_ms() - t_start;
     return PWR_OK;
+}
+
+extern "C" int pia_align(pia_ctx *c, int nreads, const char *bases, const long long *off, int *align, int *dist)
+{
+    return abi_guard([&] { return align_reads(c, nreads, bases, off, align, dist); });
 }

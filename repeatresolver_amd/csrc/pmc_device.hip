@@ -18,13 +18,16 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
+#define PWR_STAGE "pmc"
+#include "base_code.h"
+#include "dev_util.h"
+#include "four_count_tile.h"
 #include "hyper_tail.h"
 #include "pmc.h"
 
@@ -35,18 +38,6 @@
 
 static double g_ms[5] = {0, 0, 0, 0, 0};
 
-__device__ __forceinline__ int code_of(unsigned char ch)
-{
-    switch (ch) {                                                     // MC:303-330
-    case 'a': case 'A': return 0;
-    case 'c': case 'C': return 1;
-    case 'g': case 'G': return 2;
-    case 't': case 'T': return 3;
-    case '-': case '_': return 4;
-    default: return 5;
-    }
-}
-
 // first covered column of every row (W if it has none): block per row
 __global__ __launch_bounds__(256) void k_mc_rowstart(int W, const unsigned char *__restrict__ text, int *__restrict__ start)
 {
@@ -56,7 +47,7 @@ __global__ __launch_bounds__(256) void k_mc_rowstart(int W, const unsigned char 
     const unsigned char *row = text + (size_t)blockIdx.x * W;
     for (int c0 = 0; c0 < W; c0 += 256) {                            // the start is usually near the row's left end
         const int c = c0 + threadIdx.x;
-        if (c < W && code_of(row[c]) < 5) atomicMin(&s_min, c);
+        if (c < W && base_code(row[c]) < 5) atomicMin(&s_min, c);
         __syncthreads();
         if (s_min < W) break;
         __syncthreads();
@@ -77,7 +68,7 @@ __global__ __launch_bounds__(256) void k_mc_bits(int T, int W, int sc, const uns
     for (int r = 0; r < 64; ++r) {
         const int pos = w * 64 + r;
         if (pos >= T) break;
-        const int k = code_of(text[(size_t)inv[pos] * W + c]);
+        const int k = base_code(text[(size_t)inv[pos] * W + c]);
         if (k < 5) g[k] |= 1ull << r;
     }
     unsigned long long lc = 0;
@@ -145,21 +136,14 @@ __global__ __launch_bounds__(256) void k_mc_end(int W, int sc, int mincov, const
     if (tid < PMC_EI && ii0 + tid < W) jend[ii0 + tid] = s_end[tid];
 }
 
-// MC:413-434 PositiveSignificance (not inlined: the epilogue of k_mc_pairs calls it from an unrolled loop over register arrays)
-// `floor`: what the two maxima this pair could raise already hold.  The tail is at least its first term, so
-// -log10 pdf(schnitt) bounds the result from above: a pair that cannot raise either maximum is dropped before the sum
-// (after a few thousand partners every variation's maximum is past what chance co-occurrence reaches, and almost every
-// pair ends here -- the sums took 93 % of the kernel before).
-__device__ __noinline__ double d_significance(const double *__restrict__ lnf, int schnitt, int cov, int gr1, int gr2, int size1, int size2, double floor)
+// MC:413-434 PositiveSignificance: d_tail_z (hyper_tail.h) and this stage's saturated value.
+// `floor`: what the two maxima this pair could raise already hold: a pair that cannot raise either maximum is dropped before
+// the sum (after a few thousand partners every variation's maximum is past what chance co-occurrence reaches, and almost
+// every pair ends here -- the sums took 93 % of the kernel before).
+__device__ __forceinline__ double d_significance(const double *__restrict__ lnf, int schnitt, int cov, int gr1, int gr2, int size1, int size2, double floor)
 {
-    if (gr1 == 0 || gr2 == 0 || schnitt < 1) return 0.0;
-    if ((unsigned)schnitt <= (unsigned)gr2 && schnitt <= gr1 && gr1 - schnitt <= cov - gr2) {
-        const double zb = d_ln_hyper_pdf(lnf, (unsigned)schnitt, (unsigned)gr2, (unsigned)(cov - gr2), (unsigned)gr1) * -0.43429448190325182;
-        if (zb < floor - 1e-6 && zb < 97.9) return 0.0;               // (beyond 98 the value is 98 + F, which the first term does not bound)
-    }
-    double Z = -1.0 * log10(d_hyper_Q(lnf, (unsigned)(schnitt - 1), (unsigned)gr2, (unsigned)(cov - gr2), (unsigned)gr1));
-    if (isinf(Z) || Z > 99) Z = 99.0;
-    if (isinf(Z) || Z > 98.0) Z = 98.0 + 2.0 * schnitt / (2.0 * schnitt + (size1 - schnitt) + (size2 - schnitt));     // F_beta(., ., 1), MC:396-410
+    double Z = d_tail_z(lnf, schnitt, cov, gr1, gr2, floor);
+    if (Z > 98.0) Z = 98.0 + 2.0 * schnitt / (2.0 * schnitt + (size1 - schnitt) + (size2 - schnitt));     // F_beta(., ., 1), MC:396-410
     return Z;
 }
 
@@ -189,30 +173,15 @@ __global__ __launch_bounds__(PMC_NT) void k_mc_pairs(int W, int sc, int nI, cons
     if (tid < PMC_TI && s_i[tid] >= 0) { const int2 r = wr[s_i[tid] / 5]; if (r.y > r.x) { atomicMin(&s_wb, r.x); atomicMax(&s_we, r.y); } }
     if (have) { const int2 r = wr[jj]; if (r.y > r.x) { atomicMin(&s_jb, r.x); atomicMax(&s_je, r.y); } }
     __syncthreads();
-    const int wbeg = max(s_wb, s_jb), wend = min(s_we, s_je);
+    const int wbeg = max(s_wb, s_jb), wend = min(s_we, s_je), V = W * 5;
     int s[PMC_TI], g1[PMC_TI], g2[PMC_TI], cv[PMC_TI];
 #pragma unroll
     for (int a = 0; a < PMC_TI; ++a) s[a] = g1[a] = g2[a] = cv[a] = 0;
     for (int w0 = wbeg; w0 < wend; w0 += PMC_WC) {
         __syncthreads();
-        for (int t = tid; t < PMC_TI * PMC_WC; t += PMC_NT) {
-            const int a = t / PMC_WC, w = w0 + t % PMC_WC, i = s_i[a];
-            const bool ok = i >= 0 && w < wend;
-            sG[a][t % PMC_WC] = ok ? G[(size_t)w * W * 5 + i] : 0ull;
-            sL[a][t % PMC_WC] = ok ? LC[(size_t)w * W + i / 5] : 0ull;
-        }
+        tile_stage<PMC_TI, PMC_WC, PMC_NT>(sG, sL, s_i, G, LC, V, W, w0, wend, tid);
         __syncthreads();
-        if (have) {
-            const int wn = min(PMC_WC, wend - w0);
-            for (int w = 0; w < wn; ++w) {
-                const unsigned long long gj = G[(size_t)(w0 + w) * W * 5 + j], lj = LC[(size_t)(w0 + w) * W + jj];
-#pragma unroll
-                for (int a = 0; a < PMC_TI; ++a) {
-                    const unsigned long long gi = sG[a][w], li = sL[a][w];
-                    s[a] += __popcll(gi & gj); g1[a] += __popcll(gi & lj); g2[a] += __popcll(gj & li); cv[a] += __popcll(li & lj);
-                }
-            }
-        }
+        if (have) tile_count<PMC_TI, PMC_WC>(sG, sL, G, LC, V, W, w0, wend, j, s, g1, g2, cv);
     }
     if (!have) return;
     const int sj = gsize[j];
@@ -237,31 +206,6 @@ __global__ __launch_bounds__(PMC_NT) void k_mc_pairs(int W, int sc, int nI, cons
     if (cnt) atomicAdd(npairs, (unsigned long long)cnt);
 }
 
-#define HIPC(call)                                                                     \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                        \
-            fprintf(stderr, "pmc: %s failed: %s\n", #call, hipGetErrorString(e_));    \
-            return PWR_ERR_DEVICE;                                                     \
-        }                                                                              \
-    } while (0)
-
-struct McBufs {
-    unsigned char *text = nullptr; unsigned long long *G = nullptr, *LC = nullptr, *maxc = nullptr, *npairs = nullptr;
-    int *gsize = nullptr, *cover = nullptr, *jend = nullptr, *Ivar = nullptr, *Jvar = nullptr; McTile *tiles = nullptr; double *lnf = nullptr;
-    int *start = nullptr, *inv = nullptr; int2 *wr = nullptr;
-    ~McBufs()
-    {
-        (void)hipFree(text); (void)hipFree(G); (void)hipFree(LC); (void)hipFree(maxc); (void)hipFree(npairs); (void)hipFree(gsize);
-        (void)hipFree(cover); (void)hipFree(jend); (void)hipFree(Ivar); (void)hipFree(Jvar); (void)hipFree(tiles); (void)hipFree(lnf); (void)hipFree(start); (void)hipFree(inv); (void)hipFree(wr);
-    }
-};
-
-static double now_ms()
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 extern "C" int pmc_last_timing(double *ms5)
 {
     if (!ms5) return PWR_ERR_ARG;
@@ -269,7 +213,7 @@ extern "C" int pmc_last_timing(double *ms5)
     return PWR_OK;
 }
 
-extern "C" int pmc_maxcorrs(int T, int W, const unsigned char *text, int mincov, int device, double *maxcorrs)
+static int maxcorrs_on_device(int T, int W, const unsigned char *text, int mincov, int device, double *maxcorrs)
 {
     if (T <= 0 || W <= 0 || !text || !maxcorrs || mincov < 0) return PWR_ERR_ARG;
     if (T > PMC_MAX_ROWS || W > PMC_MAX_COLUMNS) return PWR_ERR_RANGE;
@@ -277,33 +221,34 @@ extern "C" int pmc_maxcorrs(int T, int W, const unsigned char *text, int mincov,
     const double t0 = now_ms();
     const int sc = T / 64 + 1;                                                       // MC:338
     const size_t nv = (size_t)W * 5;
-    McBufs d;
-    if (hipMalloc(&d.text, (size_t)T * W) != hipSuccess || hipMalloc(&d.G, nv * sc * 8) != hipSuccess || hipMalloc(&d.LC, (size_t)W * sc * 8) != hipSuccess ||
-        hipMalloc(&d.maxc, nv * 8) != hipSuccess || hipMalloc(&d.gsize, nv * 4) != hipSuccess || hipMalloc(&d.cover, (size_t)W * 4) != hipSuccess ||
-        hipMalloc(&d.jend, (size_t)W * 4) != hipSuccess || hipMalloc(&d.npairs, 8) != hipSuccess || hipMalloc(&d.start, (size_t)T * 4) != hipSuccess ||
-        hipMalloc(&d.inv, (size_t)T * 4) != hipSuccess || hipMalloc(&d.wr, (size_t)W * sizeof(int2)) != hipSuccess) return PWR_ERR_NOMEM;
-    HIPC(hipMemcpy(d.text, text, (size_t)T * W, hipMemcpyHostToDevice));
-    HIPC(hipMemset(d.gsize, 0, nv * 4)); HIPC(hipMemset(d.cover, 0, (size_t)W * 4)); HIPC(hipMemset(d.maxc, 0, nv * 8)); HIPC(hipMemset(d.npairs, 0, 8));
+    typedef unsigned long long u64;
+    DevArena dev;
+    unsigned char *d_text = dev.put(text, (size_t)T * W);
+    u64 *d_G = dev.get<u64>(nv * sc), *d_LC = dev.get<u64>((size_t)W * sc), *d_maxc = dev.get<u64>(nv), *d_npairs = dev.get<u64>(1);
+    int *d_gsize = dev.get<int>(nv), *d_cover = dev.get<int>(W), *d_jend = dev.get<int>(W), *d_start = dev.get<int>(T), *d_inv = dev.get<int>(T);
+    int2 *d_wr = dev.get<int2>(W);
+    if (!d_text || !d_G || !d_LC || !d_maxc || !d_npairs || !d_gsize || !d_cover || !d_jend || !d_start || !d_inv || !d_wr) return dev.err;
+    HIPC(hipMemset(d_gsize, 0, nv * 4)); HIPC(hipMemset(d_cover, 0, (size_t)W * 4)); HIPC(hipMemset(d_maxc, 0, nv * 8)); HIPC(hipMemset(d_npairs, 0, 8));
     // bit positions in the order of the rows' first covered columns
-    hipLaunchKernelGGL(k_mc_rowstart, dim3(T), dim3(256), 0, 0, W, d.text, d.start);
+    hipLaunchKernelGGL(k_mc_rowstart, dim3(T), dim3(256), 0, 0, W, d_text, d_start);
     HIPC(hipGetLastError());
     std::vector<int> start(T), inv(T);
-    HIPC(hipMemcpy(start.data(), d.start, (size_t)T * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(start.data(), d_start, (size_t)T * 4, hipMemcpyDeviceToHost));
     for (int r = 0; r < T; ++r) inv[r] = r;
     std::stable_sort(inv.begin(), inv.end(), [&](int a, int b) { return start[a] < start[b]; });
-    HIPC(hipMemcpy(d.inv, inv.data(), (size_t)T * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_mc_bits, dim3((W + 255) / 256, sc), dim3(256), 0, 0, T, W, sc, d.text, d.inv, d.G, d.LC, d.gsize, d.cover);
+    HIPC(hipMemcpy(d_inv, inv.data(), (size_t)T * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_mc_bits, dim3((W + 255) / 256, sc), dim3(256), 0, 0, T, W, sc, d_text, d_inv, d_G, d_LC, d_gsize, d_cover);
     HIPC(hipGetLastError());
-    hipLaunchKernelGGL(k_mc_colrange, dim3((W + 255) / 256), dim3(256), 0, 0, W, sc, d.LC, d.wr);
+    hipLaunchKernelGGL(k_mc_colrange, dim3((W + 255) / 256), dim3(256), 0, 0, W, sc, d_LC, d_wr);
     HIPC(hipGetLastError());
     std::vector<int> gsize(nv), cover(W), jend(W);
-    HIPC(hipMemcpy(gsize.data(), d.gsize, nv * 4, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(cover.data(), d.cover, (size_t)W * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(gsize.data(), d_gsize, nv * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(cover.data(), d_cover, (size_t)W * 4, hipMemcpyDeviceToHost));
     const double t1 = now_ms();
     const size_t lds_end = (size_t)PMC_EI * sc * 8;
-    hipLaunchKernelGGL(k_mc_end, dim3((W + PMC_EI - 1) / PMC_EI), dim3(256), lds_end, 0, W, sc, mincov, d.LC, d.wr, d.jend);
+    hipLaunchKernelGGL(k_mc_end, dim3((W + PMC_EI - 1) / PMC_EI), dim3(256), lds_end, 0, W, sc, mincov, d_LC, d_wr, d_jend);
     HIPC(hipGetLastError());
-    HIPC(hipMemcpy(jend.data(), d.jend, (size_t)W * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(jend.data(), d_jend, (size_t)W * 4, hipMemcpyDeviceToHost));
     const double t2 = now_ms();
     // the relevant variations (MC:796, MC:811): i needs more than mincov / 4 and fewer than all rows, and bases in more than
     // half of its column's covered rows; j only the first two
@@ -337,23 +282,24 @@ extern "C" int pmc_maxcorrs(int T, int W, const unsigned char *text, int mincov,
             maxspan = std::max(maxspan, tiles[t].jhi - tiles[t].jlo);
         }
         if (maxspan > 0) {
-            if (hipMalloc(&d.Ivar, (size_t)nI * 4) != hipSuccess || hipMalloc(&d.Jvar, (size_t)nJ * 4) != hipSuccess ||
-                hipMalloc(&d.tiles, sizeof(McTile) * ntiles) != hipSuccess) return PWR_ERR_NOMEM;
-            HIPC(hipMemcpy(d.Ivar, Ivar.data(), (size_t)nI * 4, hipMemcpyHostToDevice));
-            HIPC(hipMemcpy(d.Jvar, Jvar.data(), (size_t)nJ * 4, hipMemcpyHostToDevice));
-            HIPC(hipMemcpy(d.tiles, tiles.data(), sizeof(McTile) * ntiles, hipMemcpyHostToDevice));
-            std::vector<double> lnf((size_t)T + 2);
-            for (int n = 0; n < T + 2; ++n) lnf[n] = std::lgamma(n + 1.0);
-            if (hipMalloc(&d.lnf, lnf.size() * 8) != hipSuccess) return PWR_ERR_NOMEM;
-            HIPC(hipMemcpy(d.lnf, lnf.data(), lnf.size() * 8, hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(k_mc_pairs, dim3(ntiles, (maxspan + PMC_NT - 1) / PMC_NT), dim3(PMC_NT), 0, 0, W, sc, nI, d.Ivar, d.Jvar, d.tiles,
-                               d.G, d.LC, d.gsize, d.jend, d.lnf, d.wr, d.maxc, d.npairs);
+            const std::vector<double> lnf = hyper_lnf_table(T);
+            const int *d_Ivar = dev.put(Ivar.data(), nI), *d_Jvar = dev.put(Jvar.data(), nJ);
+            const McTile *d_tiles = dev.put(tiles.data(), ntiles);
+            const double *d_lnf = dev.put(lnf.data(), lnf.size());
+            if (!d_Ivar || !d_Jvar || !d_tiles || !d_lnf) return dev.err;
+            hipLaunchKernelGGL(k_mc_pairs, dim3(ntiles, (maxspan + PMC_NT - 1) / PMC_NT), dim3(PMC_NT), 0, 0, W, sc, nI, d_Ivar, d_Jvar, d_tiles,
+                               d_G, d_LC, d_gsize, d_jend, d_lnf, d_wr, d_maxc, d_npairs);
             HIPC(hipGetLastError());
         }
     }
-    HIPC(hipMemcpy(maxcorrs, d.maxc, nv * 8, hipMemcpyDeviceToHost));                 // (bit patterns of non-negative doubles)
-    HIPC(hipMemcpy(&npairs, d.npairs, 8, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(maxcorrs, d_maxc, nv * 8, hipMemcpyDeviceToHost));                 // (bit patterns of non-negative doubles)
+    HIPC(hipMemcpy(&npairs, d_npairs, 8, hipMemcpyDeviceToHost));
     const double t3 = now_ms();
     g_ms[0] = t3 - t0; g_ms[1] = t1 - t0; g_ms[2] = t2 - t1; g_ms[3] = t3 - t2; g_ms[4] = (double)npairs;
     return PWR_OK;
+}
+
+extern "C" int pmc_maxcorrs(int T, int W, const unsigned char *text, int mincov, int device, double *maxcorrs)
+{
+    return abi_guard([&] { return maxcorrs_on_device(T, W, text, mincov, device, maxcorrs); });
 }

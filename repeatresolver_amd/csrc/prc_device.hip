@@ -30,6 +30,8 @@
 #include <numeric>
 #include <vector>
 
+#define PWR_STAGE "prc"
+#include "dev_util.h"
 #include "prc.h"
 
 #define RC_MAXWPL 20                // PRC_MAX_PART / (64 lanes x 32 bits)
@@ -132,32 +134,29 @@ struct prc_ctx {
     double kernel_ms = 0.0;
 };
 
-#define HIPC(call)                                                                     \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                        \
-            fprintf(stderr, "prc: %s failed: %s\n", #call, hipGetErrorString(e_));    \
-            return PWR_ERR_DEVICE;                                                     \
-        }                                                                              \
-    } while (0)
-
 // the kernel takes a base's code from two bits of its character: anything else would silently alias one of the four
 static inline bool rc_is_base(char ch)
 {
     switch (ch) { case 'a': case 'c': case 'g': case 't': case 'A': case 'C': case 'G': case 'T': return true; default: return false; }
 }
 
-extern "C" int prc_create(prc_ctx **out, const char *templ, int templ_len, int device)
+static int create(prc_ctx **out, const char *templ, int templ_len, int device)
 {
     if (!out || (!templ && templ_len) || templ_len < 0) return PWR_ERR_ARG;
     for (int y = 0; y < templ_len; ++y) if (!rc_is_base(templ[y])) return PWR_ERR_INPUT;
+    std::vector<char> copy(templ, templ + templ_len);                              // (before the context: nothing below throws)
     prc_ctx *c = new (std::nothrow) prc_ctx();
     if (!c) return PWR_ERR_NOMEM;
     c->device = device; c->T = templ_len;
-    c->templ.assign(templ, templ + templ_len);
+    c->templ.swap(copy);
     if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&c->stream) != hipSuccess) { delete c; return PWR_ERR_DEVICE; }
     *out = c;
     return PWR_OK;
+}
+
+extern "C" int prc_create(prc_ctx **out, const char *templ, int templ_len, int device)
+{
+    return abi_guard([&] { return create(out, templ, templ_len, device); });
 }
 
 extern "C" void prc_destroy(prc_ctx *c)
@@ -189,10 +188,10 @@ static void launch_rows(int wpl, dim3 grid, hipStream_t st, const uint32_t *plan
 
 struct RcBufs {                     // freed on every way out
     char *bases = nullptr; uint32_t *planes = nullptr; RcJob *jobs = nullptr; int *order = nullptr; int4 *runs = nullptr; int *counts = nullptr;
+    DevArena mem;                   // owns the six above
     hipEvent_t e0 = nullptr, e1 = nullptr;
     ~RcBufs()
     {
-        (void)hipFree(bases); (void)hipFree(planes); (void)hipFree(jobs); (void)hipFree(order); (void)hipFree(runs); (void)hipFree(counts);
         if (e0) (void)hipEventDestroy(e0);
         if (e1) (void)hipEventDestroy(e1);
     }
@@ -258,10 +257,9 @@ static int rc_rows(prc_ctx *c, int nreads, const char *bases, const long long *o
     if (hipSetDevice(c->device) != hipSuccess) return PWR_ERR_DEVICE;
     RcBufs d;
     HIPC(hipEventCreate(&d.e0)); HIPC(hipEventCreate(&d.e1));
-    if (hipMalloc(&d.bases, std::max<long long>(nb, 1)) != hipSuccess || hipMalloc(&d.planes, planes.size() * 4) != hipSuccess ||
-        hipMalloc(&d.jobs, sizeof(RcJob) * hj.size()) != hipSuccess || hipMalloc(&d.order, sizeof(int) * order.size()) != hipSuccess ||
-        hipMalloc(&d.runs, sizeof(int4) * std::max<long long>(roff, 1)) != hipSuccess || hipMalloc(&d.counts, sizeof(int) * hj.size()) != hipSuccess)
-        return PWR_ERR_NOMEM;
+    d.bases = d.mem.get<char>(nb); d.planes = d.mem.get<uint32_t>(planes.size()); d.jobs = d.mem.get<RcJob>(hj.size());
+    d.order = d.mem.get<int>(order.size()); d.runs = d.mem.get<int4>(roff); d.counts = d.mem.get<int>(hj.size());
+    if (!d.bases || !d.planes || !d.jobs || !d.order || !d.runs || !d.counts) return PWR_ERR_NOMEM;
     if (nb) HIPC(hipMemcpyAsync(d.bases, bases + b0, nb, hipMemcpyHostToDevice, c->stream));
     HIPC(hipMemcpyAsync(d.planes, planes.data(), planes.size() * 4, hipMemcpyHostToDevice, c->stream));
     HIPC(hipMemcpyAsync(d.jobs, hj.data(), sizeof(RcJob) * hj.size(), hipMemcpyHostToDevice, c->stream));
@@ -286,7 +284,7 @@ static int rc_rows(prc_ctx *c, int nreads, const char *bases, const long long *o
         if (counts[k] > hj[k].cap) { again.push_back(k); hj[k].cap = counts[k]; hj[k].roff = roff2; roff2 += counts[k]; }
     std::vector<int4> hr2((size_t)roff2);
     if (!again.empty()) {
-        int4 *runs2 = nullptr;
+        int4 *runs2 = nullptr;                                                     // (freed as soon as its runs are on the host)
         if (hipMalloc(&runs2, sizeof(int4) * roff2) != hipSuccess) return PWR_ERR_NOMEM;
         std::vector<int> counts2((size_t)njobs, 0);
         int rc = PWR_OK;
@@ -320,8 +318,8 @@ static int rc_rows(prc_ctx *c, int nreads, const char *bases, const long long *o
     return PWR_OK;
 }
 
-extern "C" int prc_occurrences(prc_ctx *c, int nreads, const char *bases, const long long *off, int parts, int overlap,
-                               double error_cutoff, long long *pos_off, int **pos)
+static int occurrences(prc_ctx *c, int nreads, const char *bases, const long long *off, int parts, int overlap, double error_cutoff,
+                       long long *pos_off, int **pos)
 {
     if (!pos_off || !pos) return PWR_ERR_ARG;
     int nq = 0, len = 0;
@@ -341,8 +339,14 @@ extern "C" int prc_occurrences(prc_ctx *c, int nreads, const char *bases, const 
     return PWR_OK;
 }
 
-extern "C" int prc_cut(prc_ctx *c, int nreads, const char *bases, const long long *off, int parts, int overlap, double error_cutoff,
-                       int *ncut, int **cuts)
+extern "C" int prc_occurrences(prc_ctx *c, int nreads, const char *bases, const long long *off, int parts, int overlap,
+                               double error_cutoff, long long *pos_off, int **pos)
+{
+    return abi_guard([&] { return occurrences(c, nreads, bases, off, parts, overlap, error_cutoff, pos_off, pos); });
+}
+
+static int cut(prc_ctx *c, int nreads, const char *bases, const long long *off, int parts, int overlap, double error_cutoff, int *ncut,
+               int **cuts)
 {
     if (!ncut || !cuts) return PWR_ERR_ARG;
     int nq = 0, len = 0;
@@ -374,4 +378,10 @@ extern "C" int prc_cut(prc_ctx *c, int nreads, const char *bases, const long lon
     }
     *cuts = out;
     return PWR_OK;
+}
+
+extern "C" int prc_cut(prc_ctx *c, int nreads, const char *bases, const long long *off, int parts, int overlap, double error_cutoff,
+                       int *ncut, int **cuts)
+{
+    return abi_guard([&] { return cut(c, nreads, bases, off, parts, overlap, error_cutoff, ncut, cuts); });
 }
