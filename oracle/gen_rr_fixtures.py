@@ -7,6 +7,9 @@ non-zero lines) and the two label files verbatim with their names.  KmeansSubdiv
 the reference exists (the build container); the GPU box sees just the fixture.
 
     python oracle/gen_rr_fixtures.py            # rewrites tests/golden/rr_reference.json.gz, byte for byte reproducible
+    python oracle/gen_rr_fixtures.py --deep     # the second case table, DEEP_LABEL_CASES of tests/deep_cases.py (more than
+                                                # 2 047 kept rows), into tests/golden/rr_deep_reference.json.gz; then
+                                                # scripts/gen_km_fixtures.py --deep adds the third label file to each record
 
 The conditions that make an exact comparison of the labels legitimate are asserted here for every case with labels (and
 again from the fixture by tests/test_rr_reference.py; rr_cases.label_conditions): no significant variation is `undecided`
@@ -77,37 +80,46 @@ def split_parts(rec):
     return sorted(k for k, v in into.items() if len(v) > 1), max(a) + 1, max(b) + 1
 
 
+REFERENCE_BUILD = "gcc -O2 -w -mcmodel=medium -Igsl_standin {MaxCorrelation,RepeatResolver}.c gsl_standin.c mc_oracle.c -lm -lpthread"
+
+
+def record(name, case):
+    """the reference's record of one case, its conditions asserted"""
+    rec = {"name": name}
+    rec.update(run_reference(case))
+    msg = f"{name}: {rec['rows']} x {rec['width']}, {len(rec['maxcorrs']['nonzero'])} non-zero MaxCorrs"
+    if case["labels"]:
+        rec["condition"], sig, und = rc.label_conditions(case, rec)
+        assert (rec["condition"] == "strict") == (name not in ("kept64", "kept65", "rel5groups")), (name, und)
+        split, n1, n2 = split_parts(rec)
+        msg += f", {sig} significant, undecided {und} ({rec['condition']}), parts {n1} -> {n2}, split {split}"
+    print(msg, flush=True)
+    return rec
+
+
+def write_fixture(path, head, cases):
+    data = json.dumps(dict(head, cases=cases), indent=0, sort_keys=True).encode()
+    with open(path, "wb") as raw, gzip.GzipFile(filename="", mode="wb", compresslevel=9, fileobj=raw, mtime=0) as f:
+        f.write(data)
+    print(f"{path}: {len(cases)} cases, {len(data)} bytes of JSON, {os.path.getsize(path)} on disk")
+
+
 def main():
     for b in (MC, RR):
         if not os.path.exists(b):
             sys.exit(f"{b} is missing: run `make -C oracle ref` where the reference sources exist")
-    cases = []
-
-    def add(name):
-        case = rc.case_input(name)
-        rec = {"name": name}
-        rec.update(run_reference(case))
-        msg = f"{name}: {rec['rows']} x {rec['width']}, {len(rec['maxcorrs']['nonzero'])} non-zero MaxCorrs"
-        if case["labels"]:
-            rec["condition"], sig, und = rc.label_conditions(case, rec)
-            assert (rec["condition"] == "strict") == (name not in ("kept64", "kept65", "rel5groups")), (name, und)
-            split, n1, n2 = split_parts(rec)
-            msg += f", {sig} significant, undecided {und} ({rec['condition']}), parts {n1} -> {n2}, split {split}"
-        print(msg, flush=True)
-        return rec
-
-    for name in rc.BUILDERS:
-        cases.append(add(name))
+    if sys.argv[1:] == ["--deep"]:
+        import deep_cases as dc
+        cases = [record(name, dc.case_input(name)) for name in dc.DEEP_LABEL_CASES]
+        write_fixture(dc.FIXTURE, {"generator": "oracle/gen_rr_fixtures.py --deep, then scripts/gen_km_fixtures.py --deep",
+                                   "reference_build": REFERENCE_BUILD, "msa_name": rc.MSA_NAME}, cases)
+        return
+    cases = [record(name, rc.case_input(name)) for name in rc.BUILDERS]
     by = {c["name"]: c for c in cases}
     assert split_parts(by["stretched"])[0] == [40]                    # one pass of 64 parts is not enough: 192 parts ...
     deep = split_parts(by["stretched_deep"])[0]
     assert deep and all(k >= rc.KERNEL_TILE for k in deep), deep      # ... and here the splits lie beyond the first pass
-    data = json.dumps({"generator": "oracle/gen_rr_fixtures.py",
-                       "reference_build": "gcc -O2 -w -mcmodel=medium -Igsl_standin {MaxCorrelation,RepeatResolver}.c gsl_standin.c mc_oracle.c -lm -lpthread",
-                       "msa_name": rc.MSA_NAME, "cases": cases}, indent=0, sort_keys=True).encode()
-    with open(rc.FIXTURE, "wb") as raw, gzip.GzipFile(filename="", mode="wb", compresslevel=9, fileobj=raw, mtime=0) as f:
-        f.write(data)
-    print(f"{rc.FIXTURE}: {len(cases)} cases, {len(data)} bytes of JSON, {os.path.getsize(rc.FIXTURE)} on disk")
+    write_fixture(rc.FIXTURE, {"generator": "oracle/gen_rr_fixtures.py", "reference_build": REFERENCE_BUILD, "msa_name": rc.MSA_NAME}, cases)
 
 
 if __name__ == "__main__":

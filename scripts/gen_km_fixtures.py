@@ -7,6 +7,8 @@ its text verbatim; for a new case also the MaxCorrsOf_ non-zero lines and the tw
 holds them for the others.  Runs only where the reference exists.
 
     python scripts/gen_km_fixtures.py          # rewrites the fixture, byte for byte reproducible
+    python scripts/gen_km_fixtures.py --deep   # after oracle/gen_rr_fixtures.py --deep: adds the KmeansSubdivisionOf_ file to every
+                                               # record of tests/golden/rr_deep_reference.json.gz (tests/deep_cases.py)
 
 The existing cases are fed their recorded MaxCorrsOf_ lines (rr_cases.maxcorrs_lines); for the new ones the reference's
 own MaxCorrelation writes the file first.  The condition for an exact comparison is asserted per case: the label conditions of
@@ -33,8 +35,9 @@ RR = os.path.join(ROOT, "oracle", "_ref", "repeat_resolver")
 MARGIN = 1e-8
 
 
-def run_reference(name):
-    case = kc.case_input(name)
+def run_reference(name, case=None, old=None):
+    """case / old: an input and its record of the first stages from elsewhere than km_cases / rr_reference.json.gz"""
+    case = case or kc.case_input(name)
     rows, new = case["rows"], name in kc.NEW_BUILDERS
     args = kc.rr_args(case)
     rec = {"name": name, "input_sha256": rc.input_sha256(rows), "args": args, "rows": len(rows), "width": len(rows[0]),
@@ -50,7 +53,7 @@ def run_reference(name):
             rec["maxcorrs"] = {"lines": len(lines), "nonzero": [[i, l] for i, l in enumerate(lines) if l != "0.000000"]}
         else:
             with open(mc_path, "w") as f:
-                f.write("".join(l + "\n" for l in rc.maxcorrs_lines(rc.load_fixture()[name])))
+                f.write("".join(l + "\n" for l in rc.maxcorrs_lines(old or rc.load_fixture()[name])))
         subprocess.run([RR] + args, cwd=td, capture_output=True, check=True, timeout=600)
         names = sorted(n for n in os.listdir(td) if "SubdivisionOf_" in n)
         assert len(names) == 3 and names[1].startswith("Kmeans"), names
@@ -60,7 +63,7 @@ def run_reference(name):
         rec["dropoff"] = {"file": names[0], "text": text[names[0]]}
         rec["reldrop"] = {"file": names[2], "text": text[names[2]]}
     else:
-        old = rc.load_fixture()[name]
+        old = old or rc.load_fixture()[name]
         assert text[names[0]] == old["dropoff"]["text"] and text[names[2]] == old["reldrop"]["text"], name
     return rec, case
 
@@ -74,9 +77,32 @@ def condition(rec, first, case):
     return km.margin(got["eligible"], win.cutoff), got
 
 
+def main_deep():
+    """the third label file of every record oracle/gen_rr_fixtures.py --deep wrote, fed that record's MaxCorrsOf_ lines"""
+    import deep_cases as dc
+    with gzip.open(dc.FIXTURE, "rb") as f:
+        fixture = json.load(f)
+    for first in fixture["cases"]:
+        name = first["name"]
+        rec, case = run_reference(name, dc.case_input(name), first)
+        assert rec["input_sha256"] == first["input_sha256"] and rec["args"] == first["args"]["rr"]
+        margin, got = condition(rec, first, case)
+        same = sd.subdivision_bytes(got["labels"]) == rec["kmeans"]["text"].encode()
+        print(f"{name}: {rec['rows']} x {rec['width']}, parts {got['parts_before']} -> {got['parts']}, eligible {len(got['eligible'])}, "
+              f"varzahl {[p['varzahl'] for p in got['eligible']][:8]}, margin {margin:.3g}, checker {'equal' if same else 'DIFFERS'}", flush=True)
+        assert margin > MARGIN, f"{name}: a pair {margin} from the cutoff: choose another seed"
+        first["kmeans"] = rec["kmeans"]
+    data = json.dumps(fixture, indent=0, sort_keys=True).encode()
+    with open(dc.FIXTURE, "wb") as raw, gzip.GzipFile(filename="", mode="wb", compresslevel=9, fileobj=raw, mtime=0) as f:
+        f.write(data)
+    print(f"{dc.FIXTURE}: {len(fixture['cases'])} cases, {len(data)} bytes of JSON, {os.path.getsize(dc.FIXTURE)} on disk")
+
+
 def main():
     if not os.path.exists(RR) or not os.path.exists(MC):
         sys.exit(f"{RR} is missing: run `make -C oracle ref` where the reference sources exist")
+    if sys.argv[1:] == ["--deep"]:
+        return main_deep()
     cases, vars_only = [], []
     for name in kc.case_names():
         rec, case = run_reference(name)

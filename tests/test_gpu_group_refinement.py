@@ -117,6 +117,9 @@ CASES = {
     "window": lambda: (windowed_msa(), 120, 330, 12),
     "bis_beyond": lambda: (windowed_msa(seed=22, T=80, W=300), 60, 5000, 12),
 }
+# inputs that other test files send through checked() / compare() and that no test here is parametrised over: the layout of
+# CASES, filled by the file that owns them (tests/deep_cases.py)
+EXTRA_CASES = {}
 
 
 def fixture_cases():
@@ -132,8 +135,8 @@ def fixture_cases():
 @functools.lru_cache(maxsize=None)
 def checked(name):
     """(rows, maxcorrs of the whole MSA, von, bis, cov, the checker's result): computed once per process"""
-    if name in CASES:
-        rows, von, bis, cov = CASES[name]()
+    if name in CASES or name in EXTRA_CASES:
+        rows, von, bis, cov = (CASES.get(name) or EXTRA_CASES[name])()
     else:
         rows = split_rows(golden_output(name))                       # their middle 600 columns, the window in the middle of those
         c0 = max(0, len(rows[0]) // 2 - 300)

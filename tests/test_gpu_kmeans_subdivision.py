@@ -20,9 +20,10 @@ from test_kmeans_subdivision import CASES, CLI, checker_run
 from test_subdivision import as_refined
 
 
-def compare(name):
+def compare(name, run=None):
+    """run: the tuple of checker_run for an input of another fixture (tests/deep_cases.py)"""
     from repeatresolver_amd.kmeans_subdivision import kmeans_subdivide
-    rec, first, case, win, ref, sub, exp = checker_run(name)
+    rec, first, case, win, ref, sub, exp = run or checker_run(name)
     got = kmeans_subdivide(case["rows"], as_refined(ref), sub["reldrop_labels"], case["von"], case["bis"], case["cov"], debug_pairs=True)
     parts = exp["eligible"]
     worst = 0.0
