@@ -20,7 +20,9 @@
  *
  * At the end: the whole repeat.  pgr_msa_* keep the MSA on the device, read every window there (pgr_win_device.hip) and run
  * the three stages per window in one call; pgr_connect chains the windows' labellings into the connection matrix of the
- * reference's SimDataAssessment.py (ProbabilityMatrix, MultiStepResolution: "SDA:" 359-391).
+ * reference's SimDataAssessment.py (ProbabilityMatrix, MultiStepResolution: "SDA:" 359-391).  Last, for a labelling of the
+ * rows, the consensus of every part and the differences between them on the device copy (pgr_cons_device.hip), and on those
+ * the resolvability count of the reference's TransposonAssessment.py ("TA:").
  *
  * Floating point: only the ranking of the clique's candidates touches it (the hypergeometric tail, as in pmc.h: equal to
  * the reference's up to rounding, not bit for bit) and, in the k-means stage, the choice of the variables (both tails, against
@@ -237,6 +239,48 @@ typedef struct {
  * one matrix each way.  PWR_ERR_ARG: nres < 2, rows <= 0, a label below -1, a labelling without a label >= 0. */
 int pgr_connect(int nres, int rows, const int *labels, pgr_connection *out);
 void pgr_connection_free(pgr_connection *out);
+
+/* ---- per-copy consensus and resolvability on the device-resident MSA (TransposonAssessment.py, "TA:") ---- */
+/* For a labelling of the rows: the symbol counts of every part in every column of the window, their consensus, and the
+ * number of columns in which the consensus of two parts differ.  Symbols as base_code.h codes them (a c g t 0 .. 3, '-' and '_'
+ * 4; anything else is blank and counted nowhere: counter[5] = 0, TA:90).  The parts are the labels that occur, ascending
+ * (GroupMaker, TA:159-160); rows labelled -1 belong to none.  The consensus of a column is the FIRST code with the largest
+ * count (np.argmax, TA:91): a beats c on a tie, any base beats '-'; where no row of the part has a symbol (depth 0) it is
+ * code 0, as in the reference.  A column x is selected when max(maxcorrs_full[5x .. 5x + 4]) > cutoff (TA:263, TA:157),
+ * compared on the host in doubles; maxcorrs_full = NULL selects every column of the window.  diff is Diff (TA:94-95) over the
+ * selected columns -- a consensus is never blank, so a Hamming distance --, diff_all the same over all columns. */
+#define PGR_CS_TILE 1024         /* window columns per work-group of the counts kernel (pgr_cons_device.hip) */
+#define PGR_CS_ROWS 255          /* rows of one part per work-group (8-bit counters): a longer part is spread over several, added by atomics */
+#define PGR_CS_SCRATCH_INTS (1 << 25)   /* most count entries (parts * columns * 5) held on the device at a time: a wider
+                                         * window is worked through in column ranges, a whole number of tiles each */
+typedef struct {
+    int rows, von, bis, width;        /* window [von, bis] inclusive as elsewhere in this header; width = bis + 1 - von */
+    int parts;                        /* labels that occur */
+    int *part_label, *part_rows;      /* [parts] ascending labels, rows of each */
+    unsigned char *consensus;         /* [parts][width] codes 0..4 */
+    int *depth;                       /* [parts][width] rows of the part with a symbol there: the sum of the five counts */
+    int *counts;                      /* [parts][width][5], NULL unless asked for */
+    int nselected; int *selected;     /* absolute columns, ascending */
+    int *diff, *diff_all;             /* [parts][parts] */
+} pgr_consensus;
+
+/* von = bis = -1: the whole width.  PWR_ERR_ARG: a label below -1, von > bis, an end outside the text, no row with a label
+ * >= 0; PWR_ERR_RANGE: a label >= PGR_MAX_ROWS; PWR_ERR_NOMEM: the host cannot hold the result, or the device not even one
+ * tile of columns of every part.  want_counts != 0 fills counts.  *out holds malloc'ed arrays (empty after a failure):
+ * release them with pgr_consensus_free.  All results are integers and do not depend on the order of the atomics. */
+int pgr_msa_consensus(pgr_msa *h, const int *labels, int von, int bis, const double *maxcorrs_full /* width*5 or NULL */,
+                      double cutoff, int want_counts, pgr_consensus *out);
+void pgr_consensus_free(pgr_consensus *out);
+/* Duration of the last pgr_msa_consensus, ms: [0] all, [1] the sort by part and the upload of order, [2] the counts kernel,
+ * [3] the consensus and diff kernels, [4] the downloads.  (Kept per process, not per call.) */
+int pgr_last_consensus_timing(double *ms5);
+
+/* ---- host side, plain C (pgr_host.c) ---- */
+/* Resolvability (TA:97-119) on diff[parts][parts]: unique11[t], t = 0 .. 10, = the parts whose smallest diff to any other
+ * part is > t; min_diff[parts] that smallest diff; last_diff[parts] what the reference itself returns, the diff to the LAST
+ * other part visited (TA:112 appends `diff`, not `mindiff`).  PWR_ERR_ARG: fewer than two parts (the reference stops on an
+ * undefined name). */
+int pgr_resolvability(int parts, const int *diff, int *unique11, int *min_diff, int *last_diff);
 
 #ifdef __cplusplus
 }

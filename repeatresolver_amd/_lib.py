@@ -43,7 +43,14 @@ PGR_EXPORTS = ["pgr_refine", "pgr_free", "pgr_last_timing", "pgr_read_window", "
                "pgr_last_subdivision_timing", "pgr_dropoff_subdivision", "pgr_compress_labels", "pgr_complete_labels",
                "pgr_write_subdivision", "pgr_subdivision_name", "pgr_kmeans_subdivide", "pgr_kmeans_free", "pgr_kmeans_subdivide_pairs",
                "pgr_last_kmeans_timing", "pgr_kmeans_reassign", "pgr_msa_open", "pgr_msa_close", "pgr_msa_window", "pgr_msa_resolve",
-               "pgr_resolution_free", "pgr_last_resolve_timing", "pgr_connect", "pgr_connection_free"]
+               "pgr_resolution_free", "pgr_last_resolve_timing", "pgr_connect", "pgr_connection_free", "pgr_msa_consensus",
+               "pgr_consensus_free", "pgr_last_consensus_timing", "pgr_resolvability"]
+
+# constants of include/pgr.h that tests and scripts cite (pgr_cons_device.hip)
+PGR_MAX_ROWS = 30000
+PGR_CS_TILE = 1024            # window columns per work-group of k_cs_counts
+PGR_CS_ROWS = 255             # rows of one part per work-group
+PGR_CS_SCRATCH_INTS = 1 << 25  # count entries on the device at a time: a wider window goes through in column ranges
 
 
 class PgrWindow(ctypes.Structure):
@@ -96,6 +103,14 @@ class PgrConnection(ctypes.Structure):
     _fields_ = [("k_first", ctypes.c_int), ("k_last", ctypes.c_int), ("matrix", ctypes.POINTER(ctypes.c_double)),
                 ("best", ctypes.POINTER(ctypes.c_int)), ("confidence", ctypes.POINTER(ctypes.c_double)),
                 ("mutual", ctypes.POINTER(ctypes.c_int))]
+
+
+class PgrConsensus(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_int), ("von", ctypes.c_int), ("bis", ctypes.c_int), ("width", ctypes.c_int),
+                ("parts", ctypes.c_int), ("part_label", ctypes.POINTER(ctypes.c_int)), ("part_rows", ctypes.POINTER(ctypes.c_int)),
+                ("consensus", ctypes.POINTER(ctypes.c_ubyte)), ("depth", ctypes.POINTER(ctypes.c_int)),
+                ("counts", ctypes.POINTER(ctypes.c_int)), ("nselected", ctypes.c_int), ("selected", ctypes.POINTER(ctypes.c_int)),
+                ("diff", ctypes.POINTER(ctypes.c_int)), ("diff_all", ctypes.POINTER(ctypes.c_int))]
 
 
 _lib = None
@@ -288,5 +303,13 @@ def load():
     lib.pgr_connect.argtypes = [ci, ci, pi, ctypes.POINTER(PgrConnection)]
     lib.pgr_connection_free.restype = None
     lib.pgr_connection_free.argtypes = [ctypes.POINTER(PgrConnection)]
+    lib.pgr_msa_consensus.restype = ci
+    lib.pgr_msa_consensus.argtypes = [vp, pi, ci, ci, pd, ctypes.c_double, ci, ctypes.POINTER(PgrConsensus)]
+    lib.pgr_consensus_free.restype = None
+    lib.pgr_consensus_free.argtypes = [ctypes.POINTER(PgrConsensus)]
+    lib.pgr_last_consensus_timing.restype = ci
+    lib.pgr_last_consensus_timing.argtypes = [pd]
+    lib.pgr_resolvability.restype = ci
+    lib.pgr_resolvability.argtypes = [ci, pi, pi, pi, pi]
     _lib = lib
     return lib

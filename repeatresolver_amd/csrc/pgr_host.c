@@ -391,3 +391,22 @@ int pgr_connect(int nres, int rows, const int *labels, pgr_connection *out)
     }
     return PWR_OK;
 }
+
+/* Resolvability (TransposonAssessment.py:97-119, "TA:") on the diff matrix of pgr_msa_consensus */
+int pgr_resolvability(int parts, const int *diff, int *unique11, int *min_diff, int *last_diff)
+{
+    if (parts < 2 || !diff || !unique11 || !min_diff || !last_diff) return PWR_ERR_ARG;   /* (TA:112 reads a `diff` never set) */
+    for (int t = 0; t < 11; t++) unique11[t] = 0;
+    for (int k = 0; k < parts; k++) {
+        int mindiff = 1000000, last = 0;                                              /* TA:104 */
+        for (int kk = 0; kk < parts; kk++) {
+            if (kk == k) continue;
+            last = diff[(size_t)k * parts + kk];                                      /* TA:107 */
+            if (last < mindiff) mindiff = last;
+        }
+        for (int t = 0; t < 11; t++) unique11[t] += mindiff > t;                      /* TA:110-114: unique[t] survives while every diff > t */
+        min_diff[k] = mindiff;
+        last_diff[k] = last;                                                          /* TA:112 appends diff, not mindiff */
+    }
+    return PWR_OK;
+}

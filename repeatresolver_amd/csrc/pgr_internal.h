@@ -4,6 +4,12 @@
 
 #include "pgr.h"
 
+/* The MSA resident on the device (pgr_msa_open, pgr_win_device.hip); pgr_cons_device.hip reads the text too */
+struct pgr_msa {
+    int rows, width, device;
+    unsigned char *text;              /* [rows][width] on the device */
+};
+
 /* A window's sets on the device, word-major as k_gr_cliques and k_gr_votes read them */
 typedef struct {
     int rows, kept_rows, von, bis, width, sc;

@@ -24,11 +24,6 @@
 #include "pgr.h"
 #include "pgr_internal.h"
 
-struct pgr_msa {
-    int rows, width, device;
-    unsigned char *text;                                               // [rows][width] on the device
-};
-
 static double g_rs_ms[7] = {0, 0, 0, 0, 0, 0, 0};
 
 __global__ __launch_bounds__(256) void k_win_kept(int rows, long long width, int von, int bis, const unsigned char *__restrict__ text,
@@ -146,7 +141,8 @@ extern "C" int pgr_msa_open(int rows, int width, const unsigned char *text, int 
     if (!m) return PWR_ERR_NOMEM;
     m->rows = rows; m->width = width; m->device = device;
     const size_t bytes = (size_t)rows * (size_t)width;
-    if (hipMalloc(&m->text, bytes) != hipSuccess) { (void)hipGetLastError(); free(m); return PWR_ERR_NOMEM; }
+    // (bytes + 3: a whole number of 32-bit words, k_cs_counts of pgr_cons_device.hip reads the text as words)
+    if (hipMalloc(&m->text, bytes + 3) != hipSuccess) { (void)hipGetLastError(); free(m); return PWR_ERR_NOMEM; }
     if (hipMemcpy(m->text, text, bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(m->text); free(m); return PWR_ERR_DEVICE; }
     g_rs_ms[0] = now_ms() - t0;
     *h = m;

@@ -114,17 +114,32 @@ def clustered(rows, von=None, bis=None, cov: int = 30, cutoff: float = 0.0, devi
     return sub, kmeans_subdivide(rows, refined, sub, von, bis, cov, device)
 
 
-def resolved(rows, parts: int = 6, coverage: float = 0.90, cov: int = 30, cutoff: float = 0.0, device: int = 0):
-    """The whole repeat as the reference README runs it: MaxCorrelation, Window.py's boundaries (`parts` windows over the
-    columns covered by at least `coverage` of the mean), RepeatResolver on every window [b_p, b_{p+1}] from one device copy
-    of the MSA, and the connection of the windows' k-means labellings.  Returns (boundaries, [resolution.ResolvedWindow],
-    resolution.Connection or None for a single window)."""
+def _resolved(rows, parts, coverage, cov, cutoff, device, copies):
     from .max_correlation import max_correlations
-    from .resolution import connect, open_msa, resolve
+    from .resolution import connect, consensus, open_msa, resolve
     from .window import window_boundaries
     sites = window_boundaries(rows, coverage, parts)
     mc = max_correlations(rows, cov, device)
     with open_msa(rows, device) as msa:
         windows = resolve(msa, mc, sites, cov, cutoff)
+        cons = [consensus(msa, w.kmeans_labels, w.von, w.bis, mc, w.cutoff) if w.kept_rows > 0 else None
+                for w in windows] if copies else None
     con = connect([w.kmeans_labels for w in windows]) if len(windows) > 1 else None
-    return sites, windows, con
+    return sites, windows, con, cons
+
+
+def resolved(rows, parts: int = 6, coverage: float = 0.90, cov: int = 30, cutoff: float = 0.0, device: int = 0):
+    """The whole repeat as the reference README runs it: MaxCorrelation, Window.py's boundaries (`parts` windows over the
+    columns covered by at least `coverage` of the mean), RepeatResolver on every window [b_p, b_{p+1}] from one device copy
+    of the MSA, and the connection of the windows' k-means labellings.  Returns (boundaries, [resolution.ResolvedWindow],
+    resolution.Connection or None for a single window)."""
+    return _resolved(rows, parts, coverage, cov, cutoff, device, False)[:3]
+
+
+def resolved_copies(rows, parts: int = 6, coverage: float = 0.90, cov: int = 30, cutoff: float = 0.0, device: int = 0):
+    """resolved, and what a repeat is resolved for: the sequence of every copy.  Returns resolved's three values and a list with
+    one resolution.Consensus per window (None for a window that keeps no row), made from the same device copy of the MSA for the
+    window's k-means labels: resolution.consensus(msa, w.kmeans_labels, w.von, w.bis, maxcorrs, w.cutoff), the selected columns
+    being those over the cutoff the window was resolved with (RR:3977).  Consensus.sequences() and resolution.write_copies
+    turn it into sequences."""
+    return _resolved(rows, parts, coverage, cov, cutoff, device, True)

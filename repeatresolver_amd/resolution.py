@@ -2,7 +2,9 @@
 [sites[p], sites[p + 1]] is read there by the HIP window reader (pgr_win_device.hip) and runs through RepeatResolver's three
 stages (RepeatResolver.c main(), RR:3948-4075, once per window as the reference README's `-f x y`, `-f y z`, ...), and the
 windows' final labellings are chained into the connection matrix of SimDataAssessment.py ("SDA:") MultiStepResolution
-(SDA:359-391).  There is no CPU path for the reader or the stages; the connection is host code in libpwr.so."""
+(SDA:359-391).  There is no CPU path for the reader or the stages; the connection is host code in libpwr.so.  `consensus`
+gives, for a labelling, every part's consensus in a window and the differences between them (pgr_cons_device.hip), on which
+`resolvability` restates TransposonAssessment.py ("TA:")."""
 import ctypes
 from dataclasses import dataclass
 
@@ -166,6 +168,153 @@ def resolution_quality(truth, labels):
     tp = fp = 0
     by_conf = [0] * 10
     for t in range(G):                                                # SDA:325-344
+        maxi, maxtt = 0.0, 0
+        for tt in range(G):
+            if m3[t, tt] > maxi:
+                maxi, maxtt = m3[t, tt], tt
+        if maxi == m3[maxtt].max():
+            if maxtt != t:
+                fp += 1
+            else:
+                tp += 1
+                for c in range(10):
+                    if maxi > c / 10.0:
+                        by_conf[c] += 1
+    return tp, fp, by_conf
+
+
+@dataclass
+class Consensus:
+    """pgr_consensus (include/pgr.h): the parts of a labelling in one window [von, bis] of the MSA"""
+    von: int
+    bis: int
+    part_label: np.ndarray       # [parts] int32, the labels that occur, ascending (GroupMaker, TA:159-160)
+    part_rows: np.ndarray        # [parts] rows of each
+    consensus: np.ndarray        # [parts, width] uint8 codes 0..4 = a c g t -; the first of the most frequent (np.argmax, TA:91)
+    depth: np.ndarray            # [parts, width] int32 rows of the part with a symbol there; 0: the code 0 stands for nothing
+    counts: object               # [parts, width, 5] int32, or None unless asked for
+    selected: np.ndarray         # absolute columns whose MaxCorrs exceed the cutoff (TA:157), ascending
+    diff: np.ndarray             # [parts, parts] int32 selected columns where two consensus differ (Diff, TA:94-95)
+    diff_all: np.ndarray         # the same over every column of the window
+
+    @property
+    def parts(self):
+        return len(self.part_label)
+
+    def sequences(self):
+        """one bytes per part: the consensus without its '-' columns, in ACGT as MMA_Auslesen writes bases"""
+        acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+        return [acgt[row[row < 4]].tobytes() for row in self.consensus]
+
+
+def _labels(msa, labels):
+    lab = np.array([-1 if x is None else x for x in labels] if not isinstance(labels, np.ndarray) else labels, dtype=np.int64)
+    if lab.shape != (msa.rows,):
+        raise ValueError("one label per row of the MSA")
+    if lab.size and (lab.max() > 2 ** 31 - 1 or lab.min() < -2 ** 31):
+        raise ValueError("labels do not fit 32 bits")
+    return np.ascontiguousarray(lab, dtype=np.int32)
+
+
+def consensus(msa: Msa, labels, von=None, bis=None, maxcorrs=None, cutoff: float = 1.0, counts: bool = False) -> Consensus:
+    """The per-part consensus of the window [von, bis] (both inclusive; None, None: the whole width) for labels[rows] (-1 or
+    None: the row is in no part; None is the empty line of a label file, TA:74-75), computed on the device copy of the MSA
+    (pgr_cons_device.hip).  maxcorrs: MaxCorrelation's vector of the whole MSA (width * 5) or None: every column is selected."""
+    lib = _lib.load()
+    if (von is None) != (bis is None):
+        raise ValueError("von and bis go together")
+    lab = _labels(msa, labels)
+    mc = None
+    if maxcorrs is not None:
+        mc = np.ascontiguousarray(maxcorrs, dtype=np.float64)
+        if mc.shape != (msa.width * 5,):
+            raise ValueError("maxcorrs must hold width * 5 values")
+    out = _lib.PgrConsensus()
+    _check(lib, lib.pgr_msa_consensus(msa.handle, lab.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), -1 if von is None else von,
+                                      -1 if bis is None else bis, None if mc is None else mc.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                      cutoff, 1 if counts else 0, ctypes.byref(out)))
+    try:
+        P, W = out.parts, out.width
+        return Consensus(von=out.von, bis=out.bis, part_label=_copy(out.part_label, (P,), np.int32), part_rows=_copy(out.part_rows, (P,), np.int32),
+                         consensus=_copy(out.consensus, (P, W), np.uint8), depth=_copy(out.depth, (P, W), np.int32),
+                         counts=_copy(out.counts, (P, W, 5), np.int32) if counts else None,
+                         selected=_copy(out.selected, (out.nselected,), np.int32), diff=_copy(out.diff, (P, P), np.int32),
+                         diff_all=_copy(out.diff_all, (P, P), np.int32))
+    finally:
+        lib.pgr_consensus_free(ctypes.byref(out))
+
+
+def last_consensus_timing():
+    lib = _lib.load()
+    t = (ctypes.c_double * 5)()
+    lib.pgr_last_consensus_timing(t)
+    return {"all_ms": t[0], "order_ms": t[1], "counts_ms": t[2], "consensus_diff_ms": t[3], "download_ms": t[4]}
+
+
+def write_copies(path, consensus: Consensus, name: str):
+    """One FASTA record per part, `>name_<von>_<bis>_copy<label> rows=<n>` and the sequence on one line.  The format is this
+    project's own: the reference writes no consensus."""
+    with open(path, "wb") as f:
+        for label, n, seq in zip(consensus.part_label, consensus.part_rows, consensus.sequences()):
+            f.write(f">{name}_{consensus.von}_{consensus.bis}_copy{int(label)} rows={int(n)}\n".encode() + seq + b"\n")
+
+
+def unique_parts(diff):
+    """Resolvability (TA:97-119) on a diff matrix: (unique[11], min_diff[parts], last_diff[parts]).  unique[t] = the parts whose
+    smallest diff to any other part is > t; last_diff is what the reference itself returns -- the diff to the last other part
+    visited, since TA:112 appends `diff`, not `mindiff`."""
+    lib = _lib.load()
+    d = np.ascontiguousarray(diff, dtype=np.int32)
+    if d.ndim != 2 or d.shape[0] != d.shape[1]:
+        raise ValueError("diff: a square matrix")
+    P = d.shape[0]
+    pi = ctypes.POINTER(ctypes.c_int)
+    unique, mind, last = np.zeros(11, dtype=np.int32), np.zeros(max(P, 1), dtype=np.int32), np.zeros(max(P, 1), dtype=np.int32)
+    _check(lib, lib.pgr_resolvability(P, d.ctypes.data_as(pi), unique.ctypes.data_as(pi), mind.ctypes.data_as(pi), last.ctypes.data_as(pi)))
+    return unique.tolist(), mind, last
+
+
+def resolvability(msa: Msa, truth, maxcorrs, start: int, ende: int, cutoff: float = 1.0):
+    """TA:262-283: how many ground-truth copies (truth[rows], -1 / None: none) have a consensus that differs from every other
+    copy's in more than 0 .. 10 of the significant columns.  start and ende are variation indices as in the name of a label
+    file: the columns are range(start / 5, ende / 5) (TA:157) -- the script is Python 2, where / on ints is floor division --,
+    so von = start // 5 and bis = ende // 5 - 1.  Returns (unique[11], parts, min_diff, last_diff)."""
+    von, bis = start // 5, ende // 5 - 1
+    if von < 0 or bis < von:
+        raise ValueError("start and ende leave no column")
+    con = consensus(msa, truth, von, bis, maxcorrs, cutoff)
+    unique, mind, last = unique_parts(con.diff)
+    return unique, con.parts, mind, last
+
+
+def transposon_resolution_quality(truth, labels):
+    """ResolutionQuality of TransposonAssessment.py (TA:162-255) in numpy.  It differs from resolution_quality (SDA:269-351)
+    in one place: a truth group is all rows of the copy, also those the labelling leaves at -1 (TA:165, TA:178; the SDA
+    script first restricts the truth to the labelled rows).  While some rows of a copy are labelled the normalisation of
+    TA:191-195 divides the size out again; a copy left out altogether keeps a zero row here, which the scan of TA:229-242
+    counts as a true positive (at no confidence level) when it is the first copy and as a false positive otherwise.  Returns
+    (true positives, false positives, [resolved copies with confidence > 0.0, 0.1, ... 0.9])."""
+    truth = np.array([-1 if x is None else x for x in truth])
+    labels = np.array([-1 if x is None else x for x in labels])
+    if truth.shape != labels.shape or truth.ndim != 1:
+        raise ValueError("one truth and one label per row")
+    if not (labels > -1).any() or not (truth > -1).any():
+        raise ValueError("no row is labelled")
+    copies = np.unique(truth[truth > -1])                             # GroupMaker (TA:159-160, TA:165)
+    G, K = len(copies), int(labels.max()) + 1
+    counts = np.zeros((G, K))
+    for g, c in enumerate(copies):
+        counts[g] = np.bincount(labels[(truth == c) & (labels > -1)], minlength=K)
+    size1 = np.array([(truth == c).sum() for c in copies], dtype=float)
+    m1 = counts / size1[:, None]                                      # TA:177-180
+    size = np.bincount(labels[labels > -1], minlength=K).astype(float)     # Resolution.count(ttt), TA:183
+    m2 = np.divide(counts.T, size[:, None], out=np.zeros((K, G)), where=size[:, None] > 0)   # TA:182-186
+    m3 = m1 @ m2                                                      # TA:188
+    s = m3.sum(axis=1, keepdims=True)
+    m3 = np.divide(m3, s, out=m3.copy(), where=s > 0)                 # TA:191-195
+    tp = fp = 0
+    by_conf = [0] * 10
+    for t in range(G):                                                # TA:229-248
         maxi, maxtt = 0.0, 0
         for tt in range(G):
             if m3[t, tt] > maxi:
