@@ -22,7 +22,8 @@
  * the three stages per window in one call; pgr_connect chains the windows' labellings into the connection matrix of the
  * reference's SimDataAssessment.py (ProbabilityMatrix, MultiStepResolution: "SDA:" 359-391).  Last, for a labelling of the
  * rows, the consensus of every part and the differences between them on the device copy (pgr_cons_device.hip), and on those
- * the resolvability count of the reference's TransposonAssessment.py ("TA:").
+ * the resolvability count of the reference's TransposonAssessment.py ("TA:"); and the way back, every row against every
+ * part's consensus (pgr_assign_device.hip), which the reference does not have.
  *
  * Floating point: only the ranking of the clique's candidates touches it (the hypergeometric tail, as in pmc.h: equal to
  * the reference's up to rounding, not bit for bit) and, in the k-means stage, the choice of the variables (both tails, against
@@ -281,6 +282,48 @@ int pgr_last_consensus_timing(double *ms5);
  * other part visited (TA:112 appends `diff`, not `mindiff`).  PWR_ERR_ARG: fewer than two parts (the reference stops on an
  * undefined name). */
 int pgr_resolvability(int parts, const int *diff, int *unique11, int *min_diff, int *last_diff);
+
+/* ---- every row against the consensus of every part, on the device-resident MSA (pgr_assign_device.hip) ---- */
+/* The reverse of pgr_msa_consensus: given the parts' consensus, which part does a row belong to?  THE REFERENCE HAS NO
+ * COUNTERPART: these semantics are this project's own.
+ * The window is the `width` columns from von on; codes[p][c - von] is part p's code (0 .. 4, as pgr_consensus.consensus) in
+ * the absolute column c; columns[ncolumns] are the compared columns.  With base_code as in base_code.h (a c g t in either case
+ * 0 .. 3, '-' and '_' 4, every other byte 5):
+ *   mismatches[r][p] = the number of columns c in `columns` with base_code(text[r][c]) <= 4 and
+ *                      base_code(text[r][c]) != codes[p][c - von].  A row's blank, or any other byte of code 5, is compared
+ *                      nowhere.  A gap ('-' or '_') is a symbol: it matches code 4 and nothing else.
+ *   compared[r]      = the number of columns c in `columns` with base_code(text[r][c]) <= 4: the same for every part.
+ *   best[r]          = the part with the fewest mismatches, the lowest index among equals; second[r] the same rule over the
+ *                      other parts; best_mismatches[r] and second_mismatches[r] their counts.  Where compared[r] == 0 both
+ *                      are -1 and both counts 0; where parts == 1, second[r] is -1 and second_mismatches[r] is 0.
+ * best and second are part INDICES 0 .. parts - 1, not labels.  Everything is an integer, computed without atomics: no result
+ * depends on an order. */
+#define PGR_AS_SCRATCH_BYTES (64 << 20)   /* most device scratch per range of rows (planes + mismatch matrix) */
+#define PGR_AS_TILE 8            /* parts per work-group of the distance kernel (pgr_assign_device.hip) */
+
+typedef struct {
+    int rows, parts, ncolumns;
+    int *compared;            /* [rows] columns of `columns` at which the row has a symbol (base_code 0..4) */
+    int *best, *second;       /* [rows] part INDEX 0..parts-1, or -1 */
+    int *best_mismatches;     /* [rows] */
+    int *second_mismatches;   /* [rows] */
+    int *mismatches;          /* [rows][parts], or NULL unless asked for */
+} pgr_assignment;
+
+/* The rows go through the device in ranges of at most PGR_AS_SCRATCH_BYTES / (32 * ceil(ncolumns / 64) + 4 * parts) rows (one
+ * at least; 32 bytes per row and 64 columns of bit planes, 4 per row and part of the matrix), halved while the device refuses.
+ * PWR_ERR_ARG: a null pointer; parts < 1; width < 1; a window outside the text; a code above 4; ncolumns < 1; columns that do
+ * not ascend strictly or lie outside [von, von + width - 1] -- all refused before the device is touched.  PWR_ERR_RANGE:
+ * parts > PGR_MAX_ROWS.  PWR_ERR_NOMEM: the host cannot hold the result, or the device not even one row.  want_matrix != 0
+ * fills mismatches.  *out is zeroed first and holds malloc'ed arrays (empty after a failure): release them with
+ * pgr_assignment_free. */
+int  pgr_msa_assign(pgr_msa *h, int parts, int von, int width, const unsigned char *codes /* [parts][width], 0..4 */,
+                    int ncolumns, const int *columns /* absolute, strictly ascending, inside [von, von+width-1] */,
+                    int want_matrix, pgr_assignment *out);
+void pgr_assignment_free(pgr_assignment *out);
+/* Duration of the last pgr_msa_assign, ms: [0] all, [1] checks, part planes, upload and allocation, [2] the planes kernel,
+ * [3] the distance and best kernels, [4] the downloads.  (Kept per process, not per call.) */
+int  pgr_last_assign_timing(double *ms5);
 
 #ifdef __cplusplus
 }

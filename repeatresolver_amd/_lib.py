@@ -44,13 +44,17 @@ PGR_EXPORTS = ["pgr_refine", "pgr_free", "pgr_last_timing", "pgr_read_window", "
                "pgr_write_subdivision", "pgr_subdivision_name", "pgr_kmeans_subdivide", "pgr_kmeans_free", "pgr_kmeans_subdivide_pairs",
                "pgr_last_kmeans_timing", "pgr_kmeans_reassign", "pgr_msa_open", "pgr_msa_close", "pgr_msa_window", "pgr_msa_resolve",
                "pgr_resolution_free", "pgr_last_resolve_timing", "pgr_connect", "pgr_connection_free", "pgr_msa_consensus",
-               "pgr_consensus_free", "pgr_last_consensus_timing", "pgr_resolvability"]
+               "pgr_consensus_free", "pgr_last_consensus_timing", "pgr_resolvability", "pgr_msa_assign", "pgr_assignment_free",
+               "pgr_last_assign_timing"]
 
 # constants of include/pgr.h that tests and scripts cite (pgr_cons_device.hip)
 PGR_MAX_ROWS = 30000
 PGR_CS_TILE = 1024            # window columns per work-group of k_cs_counts
 PGR_CS_ROWS = 255             # rows of one part per work-group
 PGR_CS_SCRATCH_INTS = 1 << 25  # count entries on the device at a time: a wider window goes through in column ranges
+# (pgr_assign_device.hip)
+PGR_AS_SCRATCH_BYTES = 64 << 20  # planes and mismatch matrix of one range of rows: more rows go through in several ranges
+PGR_AS_TILE = 8               # parts per work-group of k_as_dist
 
 
 class PgrWindow(ctypes.Structure):
@@ -111,6 +115,13 @@ class PgrConsensus(ctypes.Structure):
                 ("consensus", ctypes.POINTER(ctypes.c_ubyte)), ("depth", ctypes.POINTER(ctypes.c_int)),
                 ("counts", ctypes.POINTER(ctypes.c_int)), ("nselected", ctypes.c_int), ("selected", ctypes.POINTER(ctypes.c_int)),
                 ("diff", ctypes.POINTER(ctypes.c_int)), ("diff_all", ctypes.POINTER(ctypes.c_int))]
+
+
+class PgrAssignment(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_int), ("parts", ctypes.c_int), ("ncolumns", ctypes.c_int), ("compared", ctypes.POINTER(ctypes.c_int)),
+                ("best", ctypes.POINTER(ctypes.c_int)), ("second", ctypes.POINTER(ctypes.c_int)),
+                ("best_mismatches", ctypes.POINTER(ctypes.c_int)), ("second_mismatches", ctypes.POINTER(ctypes.c_int)),
+                ("mismatches", ctypes.POINTER(ctypes.c_int))]
 
 
 _lib = None
@@ -311,5 +322,11 @@ def load():
     lib.pgr_last_consensus_timing.argtypes = [pd]
     lib.pgr_resolvability.restype = ci
     lib.pgr_resolvability.argtypes = [ci, pi, pi, pi, pi]
+    lib.pgr_msa_assign.restype = ci
+    lib.pgr_msa_assign.argtypes = [vp, ci, ci, ci, vp, ci, pi, ci, ctypes.POINTER(PgrAssignment)]
+    lib.pgr_assignment_free.restype = None
+    lib.pgr_assignment_free.argtypes = [ctypes.POINTER(PgrAssignment)]
+    lib.pgr_last_assign_timing.restype = ci
+    lib.pgr_last_assign_timing.argtypes = [pd]
     _lib = lib
     return lib

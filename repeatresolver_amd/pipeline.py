@@ -114,9 +114,9 @@ def clustered(rows, von=None, bis=None, cov: int = 30, cutoff: float = 0.0, devi
     return sub, kmeans_subdivide(rows, refined, sub, von, bis, cov, device)
 
 
-def _resolved(rows, parts, coverage, cov, cutoff, device, copies):
+def _resolved(rows, parts, coverage, cov, cutoff, device, copies, recruit=None):
     from .max_correlation import max_correlations
-    from .resolution import connect, consensus, open_msa, resolve
+    from .resolution import assign, connect, consensus, open_msa, resolve
     from .window import window_boundaries
     sites = window_boundaries(rows, coverage, parts)
     mc = max_correlations(rows, cov, device)
@@ -124,8 +124,12 @@ def _resolved(rows, parts, coverage, cov, cutoff, device, copies):
         windows = resolve(msa, mc, sites, cov, cutoff)
         cons = [consensus(msa, w.kmeans_labels, w.von, w.bis, mc, w.cutoff) if w.kept_rows > 0 else None
                 for w in windows] if copies else None
+        assignments = [None if c is None else assign(msa, c) for c in cons] if recruit else None
     con = connect([w.kmeans_labels for w in windows]) if len(windows) > 1 else None
-    return sites, windows, con, cons
+    if not recruit:
+        return sites, windows, con, cons
+    recruited = [w.kmeans_labels.copy() if a is None else a.labels(*recruit, keep=w.kmeans_labels) for w, a in zip(windows, assignments)]
+    return sites, windows, con, cons, assignments, recruited, connect(recruited) if len(windows) > 1 else None
 
 
 def resolved(rows, parts: int = 6, coverage: float = 0.90, cov: int = 30, cutoff: float = 0.0, device: int = 0):
@@ -143,3 +147,19 @@ def resolved_copies(rows, parts: int = 6, coverage: float = 0.90, cov: int = 30,
     being those over the cutoff the window was resolved with (RR:3977).  Consensus.sequences() and resolution.write_copies
     turn it into sequences."""
     return _resolved(rows, parts, coverage, cov, cutoff, device, True)
+
+
+def assigned(rows, parts: int = 6, coverage: float = 0.90, cov: int = 30, cutoff: float = 0.0, device: int = 0, *, min_compared,
+             min_margin):
+    """resolved_copies, and the way back from the copies to the reads.  A window's k-means labelling covers only the rows that
+    span it; here every row of the MSA is compared with the window's per-copy consensus (resolution.assign, from the same
+    device copy of the MSA, over the window's selected columns at which every copy has a consensus).  Returns resolved_copies'
+    four values and
+      * a list with one resolution.Assignment per window (None where the window has no consensus),
+      * the recruited labellings a.labels(min_compared, min_margin, keep=w.kmeans_labels): the rows of the k-means labelling
+        keep their label, a row outside it joins the copy it is nearest to where it has at least min_compared compared columns
+        and the second nearest copy is at least min_margin mismatches further away (a window without an Assignment keeps its
+        k-means labelling),
+      * the resolution.Connection of the recruited labellings (None for a single window).
+    The two thresholds depend on the read error rate and the number of selected columns: they have no default."""
+    return _resolved(rows, parts, coverage, cov, cutoff, device, True, (min_compared, min_margin))

@@ -4,7 +4,8 @@ stages (RepeatResolver.c main(), RR:3948-4075, once per window as the reference 
 windows' final labellings are chained into the connection matrix of SimDataAssessment.py ("SDA:") MultiStepResolution
 (SDA:359-391).  There is no CPU path for the reader or the stages; the connection is host code in libpwr.so.  `consensus`
 gives, for a labelling, every part's consensus in a window and the differences between them (pgr_cons_device.hip), on which
-`resolvability` restates TransposonAssessment.py ("TA:")."""
+`resolvability` restates TransposonAssessment.py ("TA:").  `assign` is the way back: every row of the MSA, also those that do not
+span the window, against every part's consensus (pgr_assign_device.hip); the reference has no counterpart for it."""
 import ctypes
 from dataclasses import dataclass
 
@@ -249,6 +250,83 @@ def last_consensus_timing():
     t = (ctypes.c_double * 5)()
     lib.pgr_last_consensus_timing(t)
     return {"all_ms": t[0], "order_ms": t[1], "counts_ms": t[2], "consensus_diff_ms": t[3], "download_ms": t[4]}
+
+
+@dataclass
+class Assignment:
+    """pgr_assignment (include/pgr.h): every row of the MSA against the consensus of every part, over `columns`.  The
+    semantics are this project's own; the reference has no counterpart."""
+    von: int
+    bis: int
+    part_label: np.ndarray       # [parts] int32: the label that part index p stands for
+    columns: np.ndarray          # [ncolumns] int32 the compared columns, absolute, ascending
+    compared: np.ndarray         # [rows] int32 compared columns in which the row has a symbol
+    best: np.ndarray             # [rows] int32 the part INDEX with the fewest mismatches, the lowest among equals; -1: nothing compared
+    second: np.ndarray           # [rows] the same over the other parts; -1: nothing compared, or a single part
+    best_mismatches: np.ndarray  # [rows] int32
+    second_mismatches: np.ndarray
+    mismatches: object           # [rows, parts] int32, or None unless asked for
+
+    def labels(self, min_compared, min_margin, keep=None):
+        """int32 [rows]: part_label[best] where compared >= min_compared and (second == -1 or second_mismatches -
+        best_mismatches >= min_margin), -1 elsewhere; where keep (an existing labelling of the rows) is >= 0, that label stays.
+        The two thresholds depend on the read error rate and on the number of compared columns: there is no default."""
+        sure = (self.best >= 0) & (self.compared >= min_compared) & \
+            ((self.second == -1) | (self.second_mismatches - self.best_mismatches >= min_margin))
+        out = np.where(sure, self.part_label[np.maximum(self.best, 0)], -1).astype(np.int32)
+        if keep is not None:
+            keep = np.asarray(keep)
+            if keep.shape != out.shape:
+                raise ValueError("keep: one label per row")
+            out = np.where(keep >= 0, keep, out).astype(np.int32)
+        return out
+
+
+def assign_sequences(msa: Msa, von: int, codes, columns, part_label=None, matrix: bool = False) -> Assignment:
+    """pgr_msa_assign (pgr_assign_device.hip): codes [parts, width] uint8, 0 .. 4, is every part's sequence over the window
+    [von, von + width - 1]; columns: the absolute columns compared, strictly ascending; part_label: the label of every part
+    (default: its index)."""
+    lib = _lib.load()
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    if codes.ndim != 2:
+        raise ValueError("codes: [parts, width]")
+    parts, width = codes.shape
+    cols = np.ascontiguousarray(columns, dtype=np.int32)
+    if cols.ndim != 1:
+        raise ValueError("columns: a list of columns")
+    part_label = np.arange(parts, dtype=np.int32) if part_label is None else np.array(part_label, dtype=np.int32)
+    if part_label.shape != (parts,):
+        raise ValueError("one label per part")
+    out = _lib.PgrAssignment()
+    _check(lib, lib.pgr_msa_assign(msa.handle, parts, von, width, codes.ctypes.data_as(ctypes.c_void_p), len(cols),
+                                   cols.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), 1 if matrix else 0, ctypes.byref(out)))
+    try:
+        T = out.rows
+        return Assignment(von=von, bis=von + width - 1, part_label=part_label, columns=cols.copy(), compared=_copy(out.compared, (T,), np.int32),
+                          best=_copy(out.best, (T,), np.int32), second=_copy(out.second, (T,), np.int32),
+                          best_mismatches=_copy(out.best_mismatches, (T,), np.int32),
+                          second_mismatches=_copy(out.second_mismatches, (T,), np.int32),
+                          mismatches=_copy(out.mismatches, (T, parts), np.int32) if matrix else None)
+    finally:
+        lib.pgr_assignment_free(ctypes.byref(out))
+
+
+def assign(msa: Msa, con: Consensus, min_depth: int = 1, all_columns: bool = False, matrix: bool = False) -> Assignment:
+    """Every row of the MSA against the consensus of every part of `con`, over con.selected (all_columns: over every column of
+    the window), of which only the columns are kept at which EVERY part has depth >= min_depth: that makes the mismatch counts
+    of two parts comparable (min_depth = 1: every part has a consensus there).  ValueError when no column is left."""
+    cols = np.arange(con.von, con.bis + 1, dtype=np.int32) if all_columns else np.asarray(con.selected, dtype=np.int32)
+    cols = cols[(con.depth[:, cols - con.von] >= min_depth).all(axis=0)]
+    if len(cols) == 0:
+        raise ValueError("no column at which every part has the depth asked for")
+    return assign_sequences(msa, con.von, con.consensus, cols, con.part_label, matrix)
+
+
+def last_assign_timing():
+    lib = _lib.load()
+    t = (ctypes.c_double * 5)()
+    lib.pgr_last_assign_timing(t)
+    return {"all_ms": t[0], "prepare_ms": t[1], "planes_ms": t[2], "dist_best_ms": t[3], "download_ms": t[4]}
 
 
 def write_copies(path, consensus: Consensus, name: str):
