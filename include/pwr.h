@@ -163,6 +163,10 @@ void pwr_snapshot_free(pwr_snapshot *snap);
  *   "check_in_trace"
  *               1 (default): the work-groups that check the segments' starts ride in the traceback kernel's launch (k_trace_blk) instead of
  *               a launch of their own between fill and traceback; 0: their own launch
+ *   "trace_prior"
+ *               1 (default): k_trace_blk first asks, one row per lane, whether the record keeps the row where it is (arrive just left
+ *               of the base above, step diagonally to the present column); a pass that arrives at such a row in that column records
+ *               the whole run of such rows below it in one step; 0: every row of a chunk is stepped.  Same placements either way.
  *   "fail_stops"
  *               1 (default): a job whose segment check failed ends its batch (round 3's rule); 0 (experimental): it waits for its
  *               repeat like a stale row -- later rows of the batch whose band intervals are disjoint from its own commit ahead of

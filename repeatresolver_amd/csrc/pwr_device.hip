@@ -204,6 +204,7 @@ struct JobBufs {
     int gate_v2;                   // k_fill_v2 launched behind k_fill_v3: it runs only while Hdr::fallback > 0
     int *chkdone;                  // [njobs] boundaries of the job's fill that k_seg_check has been through (reset by the gather)
     int check_in_trace, trace_ny;  // the check's work-groups ride in k_trace_blk's launch, behind its trace_ny rows of work-groups (one launch less per batch)
+    int trace_prior;               // k_trace_blk takes the rows that keep their place a run at a time (`trace_prior`)
     int trace_blk;                 // this batch's traceback is k_trace_blk's (its chunk words carry the 'up' moves of every 64 rows)
     int v2_follows, f64_follows;   // this batch's launches include the stand-in k_fill_v2 / the 64-bit k_fill64 (the host adds them when the
                                    // header it last saw says they are wanted; a job that wanted one in a batch without it is repeated)
@@ -2721,6 +2722,7 @@ __global__ __launch_bounds__(TRW * 64) void k_trace_par(DState st, JobBufs jb)
                                                         // instructions, so a chunk half as long is traced in half the time: 64 -> 32 rows, 30 -> 20 us)
 #endif
 #define TB_BROKE 0x1fffffu
+#define TBP_LOOK 8                                      // columns a row's prior looks at: Way[x] .. Way[x] + 7 (rows sit ~4.5 columns apart)
 #define TB_WORD(TAG, FLAG, CNT, ARR, EXF) (((unsigned long long)((TAG) & 0x3fffu) << 50) | ((unsigned long long)(FLAG) << 48) | ((unsigned long long)((CNT) & 0x7f) << 41) | \
                                            ((unsigned long long)(((ARR) + 1) & 0xfffff) << 21) | (unsigned long long)((EXF) & 0x1fffffu))
 #define TB_MAXCOL ((1 << 20) - 4)                       // columns the word can name
@@ -2756,9 +2758,46 @@ __global__ __launch_bounds__(TB_W * 64) void k_trace_blk(DState st, JobBufs jb)
     int cnt = 0, err = 0, yexit = 0;
     bool broke = false;                                    // the last pass from the top of the chunk did not reach its bottom
 
+    // The prior (`trace_prior`): a realignment leaves most bases where they are.  For row x < L - 1 the present
+    // placement says: arrive in column Way[x+1] - 1, step to Way[x] by a diagonal move, leave in Way[x] - 1.  A step of the
+    // trace is a function of (row, column), so whether the record agrees is a property of the row alone: applied at
+    // (x, Way[x+1] - 1) the step below finds Way[x] iff, after the band clamp, the A bit is set in every column of
+    // (Way[x], ycf] and clear in Way[x], and it is a diagonal one iff the C bit is set there.  One row per lane, the words of
+    // a row's columns all in flight at once; a gap of more than TBP_LOOK columns, an arrival left of the band, anything else
+    // that does not fit: "not intact", and the row is stepped as ever.  A pass that arrives at an intact row in that very
+    // column records the whole run of intact rows below it in one assignment and goes on under the run.  (The test of a step
+    // against the prior is on the chain of every row that is NOT intact: one v_readlane of `ppri` and a compare.)
+    const int wnx = __shfl_down(wcur, 1);                  // Way[x+1] (lane TB_C - 1: the bottom row of the chunk above; lane 63 gets its own Way: never intact)
+    unsigned long long pmask = 0ull;                       // bit l: row x_lo + l is intact
+    int ppri = -2;                                         // ... and the column its prior arrives in (-2: not intact; an arrival is >= -1)
+    if (jb.trace_prior) {
+        const int xr = x_lo + lane, ya = wnx - 1;
+        const int af = max(0, wcur - H);
+        const int ycf = min(ya, af + min(B, W - af) - 1);
+        // (a run ends in a row that leaves in a column >= 0 or is row 0: no way into the 'y < 0' error from inside one)
+        bool ok = lane < TB_C && xr < L - 1 && ya >= af && ycf >= wcur && ycf - wcur < TBP_LOOK && wcur >= lo && RS >= TBP_LOOK && (wcur >= 1 || xr == 0);
+        const int i0 = ok ? (wcur - lo) % RS : 0, span = ok ? ycf - wcur : -1;
+        const uint32_t *drow = dirs + (size_t)(min(xr, L - 1) >> 4) * RS;
+        uint32_t pw[TBP_LOOK];
+#pragma unroll
+        for (int k = 0; k < TBP_LOOK; ++k) { const int i = i0 + k; pw[k] = k <= span ? drow[i >= RS ? i - RS : i] : 0u; }
+        const int sh = 15 - (xr & 15);
+        ok = ok && ((pw[0] >> sh) & 0x10001u) == 0x10000u;                      // A clear, C diag in Way[x]
+#pragma unroll
+        for (int k = 1; k < TBP_LOOK; ++k) ok = ok && (k > span || ((pw[k] >> sh) & 1u));
+        pmask = __ballot(ok);
+        ppri = ok ? ya : -2;
+    }
+    const bool prior = UNI(jb.trace_prior) != 0;
+    // 'up' moves among the recorded rows: what the chunk's word carries
+    auto ups = [&]() __attribute__((always_inline)) {
+        return (int)__builtin_popcountll(__ballot(lane < TB_C && x_lo + lane >= xrec_lo && x_lo + lane <= x_top && (ncreg & 1)));
+    };
+
     // one pass over the chunk's rows from arrival column y0: records as it goes; with check_merge it stops as soon as it
     // arrives at a recorded row in the column the record arrived in (the recorded steps below are then the true ones)
-    auto pass = [&](int y0, const bool check_merge, bool &merged) __attribute__((always_inline)) {
+    // (PRIOR: std::true_type / std::false_type -- without the prior the pass is the one of round 6, instruction for instruction)
+    auto pass_t = [&](auto PRIOR, int y0, const bool check_merge, bool &merged) __attribute__((always_inline)) {
         int x = x_top, y = y0;
         int gcur = -1, yb = 0;
         uint32_t win[4] = {0, 0, 0, 0};
@@ -2766,12 +2805,27 @@ __global__ __launch_bounds__(TB_W * 64) void k_trace_blk(DState st, JobBufs jb)
         uint32_t pre[4] = {0, 0, 0, 0};
         merged = false;
         int e = 0;
+        // at (x, y): row x is intact and y is the column its prior arrives in -> record the run of intact rows that ends in x
+        auto take_run = [&]() __attribute__((always_inline)) {
+            if constexpr (!decltype(PRIOR)::value) return false;
+            const int l = x & (TB_C - 1);
+            if (__builtin_amdgcn_readlane(ppri, l) != y) return false;
+            const unsigned long long inv = ~pmask & ((2ull << l) - 1ull);
+            const int l0 = inv ? 64 - __builtin_clzll(inv) : 0;                // the lowest row of the run
+            const bool in = lane >= l0 && lane <= l;
+            ncreg = in ? (wcur << 1) : ncreg;
+            yireg = in ? wnx - 1 : yireg;
+            y = __builtin_amdgcn_readlane(wcur, l0) - 1;
+            x = x_lo + l0 - 1;
+            return true;
+        };
         while (x >= x_lo && !e) {
-            x = UNI(x); y = UNI(y); gcur = UNI(gcur); yb = UNI(yb); gpre = UNI(gpre); ybpre = UNI(ybpre); cnt = UNI(cnt);
+            x = UNI(x); y = UNI(y); gcur = UNI(gcur); yb = UNI(yb); gpre = UNI(gpre); ybpre = UNI(ybpre);
             // ---- the common case, straight: rows of the current 16-row group whose step lies in the 64-cell part of the window
             //      that holds the current column
             while ((x >> 4) == gcur && x >= x_lo) {
                 if (check_merge && x >= xrec_lo && __builtin_amdgcn_readlane(yireg, x & (TB_C - 1)) == y) { merged = true; break; }
+                if (take_run()) continue;
                 const int af = max(0, __builtin_amdgcn_readlane(wcur, x & (TB_C - 1)) - H);
                 const int ycf = min(y, af + min(B, W - af) - 1);
                 if (y < af || ycf < yb || ycf > yb + 255) break;
@@ -2784,8 +2838,6 @@ __global__ __launch_bounds__(TB_W * 64) void k_trace_blk(DState st, JobBufs jb)
                 const int yy = yb + 64 * q0 + t;
                 const int cb = (int)((__ballot((wq >> (16 + shf)) & 1u) >> t) & 1ull);
                 const int nv = (yy << 1) | (cb ^ 1);                               // PW:1394 (c) / PW:1404 (d)
-                if (x >= xrec_lo) cnt -= __builtin_amdgcn_readlane(ncreg, x & (TB_C - 1)) & 1;
-                cnt += nv & 1;
                 ncreg = (lane == (x & (TB_C - 1))) ? nv : ncreg;
                 yireg = (lane == (x & (TB_C - 1))) ? y : yireg;
                 y = yy - cb;                                                       // diag: column to the left, up: stay
@@ -2794,6 +2846,7 @@ __global__ __launch_bounds__(TB_W * 64) void k_trace_blk(DState st, JobBufs jb)
             }
             if (merged || e || x < x_lo) break;
             if (check_merge && x >= xrec_lo && __builtin_amdgcn_readlane(yireg, x & (TB_C - 1)) == y) { merged = true; break; }
+            if (take_run()) continue;
             const int a = max(0, __builtin_amdgcn_readlane(wcur, x & (TB_C - 1)) - H);
             const int Bx = min(B, W - a);
             if (y < a) { e = 1; break; }
@@ -2854,8 +2907,6 @@ __global__ __launch_bounds__(TB_W * 64) void k_trace_blk(DState st, JobBufs jb)
             if (e) break;
             const int yy = found;
             const int nv = cbit ? (yy << 1) : ((yy << 1) | 1);                       // PW:1394 (c) / PW:1404 (d)
-            if (x >= xrec_lo) cnt -= __builtin_amdgcn_readlane(ncreg, x & (TB_C - 1)) & 1;   // replaces a recorded step
-            cnt += nv & 1;
             ncreg = (lane == (x & (TB_C - 1))) ? nv : ncreg;
             yireg = (lane == (x & (TB_C - 1))) ? y : yireg;
             y = cbit ? yy - 1 : yy;
@@ -2867,7 +2918,10 @@ __global__ __launch_bounds__(TB_W * 64) void k_trace_blk(DState st, JobBufs jb)
         if (!e && !merged) yexit = y;
         return e;
     };
-#define TB_POST(FLAG, ARR) if (lane == 0) __hip_atomic_store(&hand[c], TB_WORD(ttag, FLAG, cnt, ARR, broke ? TB_BROKE : (unsigned)(yexit + 1)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    auto pass = [&](int y0, const bool check_merge, bool &merged) __attribute__((always_inline)) {
+        return prior ? pass_t(std::true_type{}, y0, check_merge, merged) : pass_t(std::false_type{}, y0, check_merge, merged);
+    };
+#define TB_POST(FLAG, ARR) cnt = ups(); if (lane == 0) __hip_atomic_store(&hand[c], TB_WORD(ttag, FLAG, cnt, ARR, broke ? TB_BROKE : (unsigned)(yexit + 1)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 
     bool merged = false;
 #ifdef PWR_DIAG
@@ -2998,6 +3052,7 @@ __global__ __launch_bounds__(TB_W * 64) void k_trace_blk(DState st, JobBufs jb)
     // did any base of the chunk move (or open a column)?  If none of the row's does, its commit has nothing to do.
     if (__ballot(lane < TB_C && x_lo + lane < L && ncreg != (wcur << 1)) != 0ull && lane == 0) __hip_atomic_store(&m->changed, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (top || err) {
+        cnt = ups();
         if (lane == 0)
             __hip_atomic_store(&hand[c], TB_WORD(ttag, err ? 3 : 2, cnt, 0, (unsigned)(yexit + 1)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -4015,6 +4070,7 @@ struct pwr_ctx {
     int seg_budget = 0;                   // > 0: this many for all the jobs of a batch together, dealt by length (measured slower; 0: seg_rows rows each)
     int seg_minrows = 64;                 // ... none with fewer own rows than this
     int spec_inorder = 64, plan_gate_rel = 1, plan_len = 0;
+    int trace_prior = 1;                  // k_trace_blk: a run of rows whose record says 'stay where you are' is one step of a pass, not one per row (0: every row is stepped, as up to round 6)
     int check_in_trace = 1;               // the work-groups of k_seg_check ride in k_trace_blk's launch (0: a launch of their own, as up to round 4's first half)
     int fail_stops = 1, hard_rows = 1, hard_up_pm = 300, hard_down_pm = 0;   // (per mille of the bandwidth)
     int plan_slack = PLAN_SLACK, plan_evrate_x100 = (int)(PLAN_EVRATE_MAX * 100.0f);   // test hooks: the gap a row must keep to be picked ahead, the event rate above which none is
@@ -4670,6 +4726,7 @@ static int enqueue_front(pwr_ctx *c)
         if (++c->trace_epoch >= (1u << 14)) { HIPC(hipMemsetAsync(c->jb.gtr, 0, (size_t)c->njobs * c->jb.trk * 8, c->stream)); c->trace_epoch = 1; }
         c->jb.trace_tag = c->trace_epoch;
         c->jb.trace_blk = (c->par_trace == 2 && c->st.colcap < TB_MAXCOL) ? 1 : 0;
+        c->jb.trace_prior = c->trace_prior;
         if (c->jb.trace_blk) hipLaunchKernelGGL(k_trace_blk, dim3(n, c->jb.trace_ny + (c->jb.check_in_trace ? c->jb.smax - 1 : 0)), dim3(TB_W * 64), 0, c->stream, c->st, c->jb);
         else hipLaunchKernelGGL(k_trace_par, dim3(n, TRK / TRW), dim3(TRW * 64), 0, c->stream, c->st, c->jb);
     }
@@ -5100,6 +5157,7 @@ extern "C" int pwr_set_option(pwr_ctx *c, const char *key, long value)
     if (!strcmp(key, "hard_up_pm")) { if (c->on_device || value < 1 || value > 100000) return PWR_ERR_ARG; c->hard_up_pm = (int)value; return PWR_OK; }
     if (!strcmp(key, "hard_down_pm")) { if (c->on_device || value < 0 || value > 100000) return PWR_ERR_ARG; c->hard_down_pm = (int)value; return PWR_OK; }
     if (!strcmp(key, "check_in_trace")) { if (value < 0 || value > 1) return PWR_ERR_ARG; c->check_in_trace = (int)value; return PWR_OK; }
+    if (!strcmp(key, "trace_prior")) { if (value < 0 || value > 1) return PWR_ERR_ARG; c->trace_prior = (int)value; return PWR_OK; }
     if (!strcmp(key, "plan_len")) { if (value < 0 || value > 100000) return PWR_ERR_ARG; c->plan_len = (int)value; c->jb.plan_len = (int)value; return PWR_OK; }
     if (!strcmp(key, "plan_gate_rel")) { if (value < 0 || value > 1) return PWR_ERR_ARG; c->plan_gate_rel = (int)value; c->jb.plan_gate_rel = (int)value; return PWR_OK; }
     if (!strcmp(key, "spec_inorder")) { if (value < 0 || value > 64) return PWR_ERR_ARG; c->spec_inorder = (int)value; c->jb.spec_inorder = (int)value; return PWR_OK; }
@@ -5144,6 +5202,7 @@ extern "C" int pwr_get_option(pwr_ctx *c, const char *key, long *value)
     else if (!strcmp(key, "plan_gate_rel")) *value = c->plan_gate_rel;
     else if (!strcmp(key, "plan_len")) *value = c->plan_len;
     else if (!strcmp(key, "check_in_trace")) *value = c->check_in_trace;
+    else if (!strcmp(key, "trace_prior")) *value = c->trace_prior;
     else if (!strcmp(key, "hard_rows")) *value = c->hard_rows;
     else if (!strcmp(key, "hard_up_pm")) *value = c->hard_up_pm;
     else if (!strcmp(key, "hard_down_pm")) *value = c->hard_down_pm;
