@@ -4014,14 +4014,11 @@ __global__ __launch_bounds__(256) void k_rowcols(DState st, int k, int *out)
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-#define HIPC(call)                                                                     \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                        \
-            fprintf(stderr, "pwr: %s failed: %s\n", #call, hipGetErrorString(e_));    \
-            return PWR_ERR_DEVICE;                                                     \
-        }                                                                              \
-    } while (0)
+#include <climits>
+#include <memory>
+
+#define PWR_STAGE "pwr"
+#include "dev_util.h"
 
 struct pwr_ctx {
     int T = 0, B = 0, H = 0, device = 0;
@@ -4057,8 +4054,8 @@ struct pwr_ctx {
     double host_enqueue_s = 0, host_wait_s = 0;   // diagnostic: time the host spent enqueueing batches / waiting for their headers (read-only options)
     unsigned host_seq = 0;                // sequence number of the header copies the commit kernels leave in pinned memory
     int seen_fallback = 0, seen_need64 = 0;   // Hdr::fallback / need64 as the host last saw them: the batches it enqueues bring k_fill_v2 / k_fill64 along
-    unsigned trace_epoch = 0;             // k_trace_par launch counter (22 bits)
-    unsigned fill_epoch = 0;              // k_fill_v3 launch counter (15 bits; the mailboxes are cleared when it wraps)
+    int trace_epoch = 0;                  // k_trace_par launch counter (22 bits)
+    int fill_epoch = 0;                   // k_fill_v3 launch counter (15 bits; the mailboxes are cleared when it wraps)
     int wave_cols = 0;                    // 4 with 9 waves: 256-column strips also at bandwidths up to 1000, so that no wave has two strips of a DP row (experiment)
     int wp_waves = 5;                     // waves per DP of the wave-pipeline fills: 9/8/5/4/3 with 2/3/4/6/8 columns per lane (5: measured best with segments side by side)
     int one_wg = 0;                       // k_fill_v3: the waves of a segment as one work-group (hand-over through LDS); 0: one work-group per wave
@@ -4097,8 +4094,73 @@ struct pwr_ctx {
     bool snap_busy = false;
     // all device allocations, for cleanup
     std::vector<void *> allocs;
+    std::vector<void *> job_allocs;       // ... those of them that alloc_jobs made and free_jobs frees
 };
 struct pwr_snapshot { pwr_ctx *c; int rows, width; size_t bytes; };
+
+// Every option of pwr_set_option / pwr_get_option that is a field of the context, once: its key, the field, the values it
+// takes (lo .. hi; with nof > 0 only the nof values of `of`), whether it is refused once the state is on the device, and
+// the copy of it in JobBufs where the kernels read it (set with the field, and by alloc_jobs after every regrow).
+struct Option {
+    const char *key;
+    int pwr_ctx::*field;
+    long lo, hi;
+    bool host_only;
+    int JobBufs::*mirror;
+    int nof;
+    int of[6];
+};
+static const Option OPTIONS[] = {
+    // (capped: every work-group of a k_fill_v3 launch must be resident at once -- 9 of 128 threads per job -- and a
+    // window beyond what one CU-full of jobs survives is of no use anyway)
+    {"window", &pwr_ctx::window, 1, 128, true},
+    {"profile", &pwr_ctx::profile, 0, 1000000},
+    {"spec_len", &pwr_ctx::spec_len, 0, 100000},
+    {"fill", &pwr_ctx::fill_mode, 3, 4, true},
+    {"stall_test", &pwr_ctx::stall_test, 0, 1000000},
+    {"evcap", &pwr_ctx::evcap, 0, EVCAP, false, &JobBufs::evcap},
+    {"force64", &pwr_ctx::force64, 0, 1, false, &JobBufs::force64},
+    {"ptrace", &pwr_ctx::par_trace, 0, 2},
+    {"slack", &pwr_ctx::cap_slack, 0, INT_MAX, true},
+    // (test hooks: where the launch counters behind the mailbox / hand-over tags stand, so that their wrap-around can be exercised)
+    {"fill_epoch", &pwr_ctx::fill_epoch, 0, (1 << 15) - 1},
+    {"trace_epoch", &pwr_ctx::trace_epoch, 0, (1 << 14) - 1},
+    {"onewg", &pwr_ctx::one_wg, 0, 1},
+    {"fill_lds", &pwr_ctx::fill_lds, 0, 100000},
+    {"onewg_lds", &pwr_ctx::one_wg_lds, 0, 100000},
+    {"seg_rows", &pwr_ctx::seg_rows, 0, 1000000, true},
+    {"seg_align", &pwr_ctx::seg_align, 16, 64, true, &JobBufs::seg_align, 3, {16, 32, 64}},
+    {"seg_max", &pwr_ctx::seg_max, 1, SEG_MAX, true},
+    {"seg_budget", &pwr_ctx::seg_budget, 0, 100000, false, &JobBufs::seg_budget},
+    {"plan_slack", &pwr_ctx::plan_slack, 0, 1000000, false, &JobBufs::plan_slack},
+    {"hard_rows", &pwr_ctx::hard_rows, 0, 2, true, &JobBufs::hard_rows},
+    {"hard_up_pm", &pwr_ctx::hard_up_pm, 1, 100000, true},
+    {"hard_down_pm", &pwr_ctx::hard_down_pm, 0, 100000, true},
+    {"check_in_trace", &pwr_ctx::check_in_trace, 0, 1},
+    {"trace_prior", &pwr_ctx::trace_prior, 0, 1},
+    {"plan_len", &pwr_ctx::plan_len, 0, 100000, false, &JobBufs::plan_len},
+    {"plan_gate_rel", &pwr_ctx::plan_gate_rel, 0, 1, false, &JobBufs::plan_gate_rel},
+    {"spec_inorder", &pwr_ctx::spec_inorder, 0, 64, false, &JobBufs::spec_inorder},
+    {"fail_stops", &pwr_ctx::fail_stops, 0, 1, false, &JobBufs::fail_stops},
+    {"plan_evrate_x100", &pwr_ctx::plan_evrate_x100, 0, 100000000, false, &JobBufs::plan_evrate_x100},
+    {"plan_ahead", &pwr_ctx::plan_ahead, 0, 1, false, &JobBufs::plan_ahead},
+    {"seg_balance", &pwr_ctx::seg_balance, 0, 1, false, &JobBufs::seg_balance},
+    {"seg_minrows", &pwr_ctx::seg_minrows, 16, 100000, false, &JobBufs::seg_minrows},
+    {"src_start", &pwr_ctx::src_start, 0, 1, true, &JobBufs::src_start},
+    {"warm_adapt", &pwr_ctx::warm_adapt, 0, 1, true},
+    {"warm_down_pm", &pwr_ctx::warm_down_pm, 1, 1000, true},
+    {"warm_up_pm", &pwr_ctx::warm_up_pm, 1, 10000, true},
+    {"warm_min_pct", &pwr_ctx::warm_min_pct, 0, 100000, true},
+    {"warm_pct", &pwr_ctx::warm_pct, 0, 100000, true},
+    {"wave_cols", &pwr_ctx::wave_cols, 0, 4, true, nullptr, 2, {0, 4}},
+    {"waves", &pwr_ctx::wp_waves, 3, 17, true, nullptr, 6, {3, 4, 5, 8, 9, 17}},
+};
+static const Option *find_option(const char *key)
+{
+    for (const Option &o : OPTIONS)
+        if (!strcmp(key, o.key)) return &o;
+    return nullptr;
+}
 
 // The host's passes over the text (1.8 GB at benchmark scale: parse, EntAlGapper, the first tallies) are row-parallel:
 // f(r0, r1, t) for contiguous shares of the rows on up to 16 threads.
@@ -4157,15 +4219,15 @@ extern "C" int pwr_device_count(void)
     return n;
 }
 
-extern "C" int pwr_create(pwr_ctx **out, int rows, int width, const unsigned char *text, int bandwidth, int device)
+// (the entries of the C ABI that can allocate on the host run through abi_guard: they are at the end of the file)
+static int create(pwr_ctx **out, int rows, int width, const unsigned char *text, int bandwidth, int device)
 {
     if (!out || !text || rows <= 0 || width <= 0) return PWR_ERR_ARG;
     if (bandwidth < 1 || bandwidth > PWR_MAX_BANDWIDTH) return PWR_ERR_RANGE;
-    pwr_ctx *c = new (std::nothrow) pwr_ctx();
-    if (!c) return PWR_ERR_NOMEM;
+    std::unique_ptr<pwr_ctx> c(new pwr_ctx());
     c->T = rows; c->B = bandwidth; c->H = bandwidth / 2; c->device = device;   // PW:1625-1626
     c->W_host = width;
-    try { c->text.resize((size_t)rows * width); } catch (...) { delete c; return PWR_ERR_NOMEM; }
+    c->text.resize((size_t)rows * width);
     std::vector<int> bad(par_threads(rows), 0);
     par_rows(rows, [&](int r0, int r1, int t) {
         for (size_t i = (size_t)r0 * width; i < (size_t)r1 * width; ++i) {
@@ -4174,8 +4236,8 @@ extern "C" int pwr_create(pwr_ctx **out, int rows, int width, const unsigned cha
             c->text[i] = (unsigned char)s;
         }
     });
-    for (int b : bad) if (b) { delete c; return PWR_ERR_INPUT; }
-    *out = c;
+    for (int b : bad) if (b) return PWR_ERR_INPUT;
+    *out = c.release();
     return PWR_OK;
 }
 
@@ -4183,6 +4245,7 @@ static void free_device(pwr_ctx *c)
 {
     for (void *p : c->allocs) (void)hipFree(p);
     c->allocs.clear();
+    c->job_allocs.clear();
     for (auto &e : c->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     c->ev_pool.clear();
     c->ev_used = 0;
@@ -4270,17 +4333,41 @@ static void host_trim(pwr_ctx *c)
     c->W_host = n;
 }
 
-static int alloc_jobs(pwr_ctx *c, int njobs)
+// The geometry of the wave-pipeline fills: NW waves per segment (or per DP), each lane of a wave C columns of a strip of
+// 64 * C.  settle_geometry makes the options that choose it consistent ("waves" reads back what it leaves).  with_geometry
+// is the one place that turns them into the pair -- the seven pairs there are kernels for -- and calls f(NW, C) with it as
+// compile-time constants: the launches (launch_fill) instantiate their kernels from it, alloc_jobs sizes the buffers.
+static void settle_geometry(pwr_ctx *c)
 {
-    JobBufs &jb = c->jb;
     if (c->B > 1000) c->wp_waves = 9;
     if (c->wp_waves == 17 && c->fill_mode != 4) c->wp_waves = 9;          // 17 x 64 threads do not fit one work-group
     if (c->wp_waves != 9) c->wave_cols = 0;
-    const int wpC = c->wp_waves == 17 ? 1 : c->wp_waves == 8 ? 3 : c->wp_waves == 5 ? 4 : c->wp_waves == 4 ? 6 : c->wp_waves == 3 ? 8 : ((c->B <= 1024 && c->wave_cols != 4) ? 2 : 4);
-    const int NC = c->wp_waves * 64 * wpC;
+}
+template <int N> using Int = std::integral_constant<int, N>;
+template <class F>
+static void with_geometry(const pwr_ctx *c, F f)
+{
+    switch (c->wp_waves) {
+    case 17: return f(Int<17>{}, Int<1>{});
+    case 5: return f(Int<5>{}, Int<4>{});
+    case 8: return f(Int<8>{}, Int<3>{});
+    case 4: return f(Int<4>{}, Int<6>{});
+    case 3: return f(Int<3>{}, Int<8>{});
+    default: return (c->B <= 1024 && c->wave_cols != 4) ? f(Int<9>{}, Int<2>{}) : f(Int<9>{}, Int<4>{});
+    }
+}
+
+static int alloc_jobs(pwr_ctx *c, int njobs)
+{
+    JobBufs &jb = c->jb;
+    settle_geometry(c);
+    int NW = 0, C = 0;
+    with_geometry(c, [&](auto nw, auto cols) { NW = nw; C = cols; });
+    const int NC = NW * 64 * C;
+    const size_t first = c->allocs.size();                                 // (what is allocated from here on is what free_jobs gives back)
     jb.Lmax = std::max(c->Lmax, 1);
-    jb.force64 = c->force64;
-    jb.evcap = c->evcap;
+    for (const Option &o : OPTIONS)
+        if (o.mirror) jb.*o.mirror = c->*o.field;
     jb.colcap = c->st.colcap;
     jb.NC = NC;
     jb.dirstride = (size_t)((jb.Lmax + 15) / 16) * NC;
@@ -4297,18 +4384,14 @@ static int alloc_jobs(pwr_ctx *c, int njobs)
     if ((rc = dmalloc(c, &jb.newcol, (size_t)njobs * jb.Lmax))) return rc;
     if ((rc = dmalloc(c, &jb.aux, (size_t)njobs * jb.Lmax))) return rc;
     if ((rc = dmalloc(c, &jb.desc, (size_t)njobs * jb.Lmax))) return rc;
-    jb.wpNW = c->wp_waves;
-    jb.wpMS = 64 * wpC;
+    jb.wpNW = NW;
+    jb.wpMS = 64 * C;
     if ((rc = dmalloc(c, &jb.lastM, (size_t)njobs * jb.NC))) return rc;
+    // (derived from several options, or from an option and the fill mode)
     jb.smax = std::max(1, std::min(c->seg_max, SEG_MAX));
-    jb.seg_align = c->seg_align;
-    jb.seg_budget = c->seg_budget; jb.seg_minrows = c->seg_minrows; jb.seg_balance = c->seg_balance;
-    jb.spec_inorder = c->spec_inorder; jb.plan_gate_rel = c->plan_gate_rel; jb.plan_len = c->plan_len;
-    jb.fail_stops = c->fail_stops; jb.hard_rows = c->hard_rows; jb.hard_up = std::max(1, (int)((long long)c->B * c->hard_up_pm / 1000)); jb.hard_down = (int)((long long)c->B * c->hard_down_pm / 1000);
-    jb.plan_ahead = c->plan_ahead; jb.plan_slack = c->plan_slack; jb.plan_evrate_x100 = c->plan_evrate_x100;
+    jb.hard_up = std::max(1, (int)((long long)c->B * c->hard_up_pm / 1000)); jb.hard_down = (int)((long long)c->B * c->hard_down_pm / 1000);
     jb.rowids = c->d_rowids;
     jb.seg_rows = c->fill_mode == 4 ? c->seg_rows : 0;
-    jb.src_start = c->src_start;
     jb.split_rank = c->split_rank; jb.split_world = c->split_world;
     jb.warm_cols = (int)std::min<long long>((long long)c->B * c->warm_pct / 100 + 2, 1 << 20);
     jb.gstride = jb.Lmax + jb.smax * (2 * jb.warm_cols + 64);          // (a row whose check failed warms up twice as long)
@@ -4317,7 +4400,7 @@ static int alloc_jobs(pwr_ctx *c, int njobs)
     if ((rc = dmalloc(c, &jb.chk, (size_t)njobs * (SEG_MAX + 1) * 2 * NC))) return rc;
     if (hipMemsetAsync(jb.chk, 0xff, sizeof(unsigned) * (size_t)njobs * (SEG_MAX + 1) * 2 * NC, c->stream) != hipSuccess) return PWR_ERR_DEVICE;
     if (c->fill_mode == 4) {
-        const size_t nmb = (size_t)njobs * c->wp_waves * jb.gstride;
+        const size_t nmb = (size_t)njobs * NW * jb.gstride;
         if ((rc = dmalloc(c, &jb.gmb, nmb))) return rc;
         // on the stream the kernels run on (a plain hipMemset is not ordered against it) and waited for
         if (hipMemsetAsync(jb.gmb, 0, nmb * 8, c->stream) != hipSuccess ||
@@ -4348,17 +4431,16 @@ static int alloc_jobs(pwr_ctx *c, int njobs)
         hipMemsetAsync(jb.pair_left, 0, sizeof(int) * (size_t)njobs * njobs, c->stream) != hipSuccess || hipMemsetAsync(jb.plan, 0, sizeof(BatchPlan), c->stream) != hipSuccess ||
         hipMemsetAsync(jb.sev, 0, sizeof(CommitEv), c->stream) != hipSuccess || hipMemsetAsync(jb.ticket, 0, 16, c->stream) != hipSuccess) return PWR_ERR_DEVICE;
     if (hipMemset(jb.meta, 0, sizeof(JobMeta) * njobs) != hipSuccess) return PWR_ERR_DEVICE;
+    c->job_allocs.assign(c->allocs.begin() + first, c->allocs.end());
     c->njobs = njobs;
     return PWR_OK;
 }
 
 static void free_jobs(pwr_ctx *c)
 {
-    JobBufs &jb = c->jb;
-    dfree(c, jb.meta); dfree(c, jb.way); dfree(c, jb.g64); dfree(c, jb.gpart); dfree(c, jb.rec2); dfree(c, jb.mark); dfree(c, jb.mark2);
-    dfree(c, jb.dirs); dfree(c, jb.newcol); dfree(c, jb.aux); dfree(c, jb.desc); dfree(c, jb.lastM); dfree(c, jb.gmb); dfree(c, jb.seg); dfree(c, jb.chk); dfree(c, jb.gtr); dfree(c, jb.diag); dfree(c, c->d_jobrows);
-    dfree(c, jb.cjob); dfree(c, jb.chg); dfree(c, jb.evkey); dfree(c, jb.evdl); dfree(c, jb.insidx); dfree(c, jb.pair_cf); dfree(c, jb.pair_left); dfree(c, jb.plan); dfree(c, jb.sev); dfree(c, jb.freed); dfree(c, jb.ticket); dfree(c, jb.chkdone);
-    jb = JobBufs{};
+    for (void *p : c->job_allocs) dfree(c, p);
+    c->job_allocs.clear();
+    c->jb = JobBufs{};
     c->d_jobrows = nullptr;
     c->njobs = 0;
 }
@@ -4607,12 +4689,12 @@ static int launch_fill(pwr_ctx *c, int njobs)
     if (c->fill_mode == 4) {
         // one work-group (worker + fetcher wave) per wave of the pipeline; grid.x = 8 keeps the work-groups of a DP
         // on one XCD (work-groups go to the XCDs round-robin by linear id)
-        if (++c->fill_epoch >= (1u << 15)) {
+        if (++c->fill_epoch >= (1 << 15)) {
             const size_t nmb = (size_t)c->njobs * c->wp_waves * c->jb.gstride;
             HIPC(hipMemsetAsync(c->jb.gmb, 0, nmb * 8, c->stream));
             c->fill_epoch = 1;
         }
-        c->jb.tagbase = c->fill_epoch << 17;
+        c->jb.tagbase = (unsigned)c->fill_epoch << 17;
         c->jb.njobs_launched = njobs;
         c->jb.stall_test = c->stall_test > 0 ? 1 : 0;
         c->jb.v2_follows = (c->seen_fallback > 0 && c->wp_waves != 17) ? 1 : 0;
@@ -4623,20 +4705,17 @@ static int launch_fill(pwr_ctx *c, int njobs)
         if (wg1) {
             // the waves of a segment as one work-group (LDS hand-over); "onewg_lds" bytes of dynamic LDS on top keep other
             // work-groups off the segment's compute unit (experiment: a CU to itself, one wave per SIMD with waves = 4)
+            // (wg1 leaves out the two pairs that have no such kernel: 17 waves, and 9 waves with strips of 256 columns)
             const size_t pad = (size_t)c->one_wg_lds;
-            if (c->wp_waves == 5) hipLaunchKernelGGL((k_fill_v3<5, 4, true>), dim3(nv), dim3(5 * 64), pad, c->stream, c->st, c->jb);
-            else if (c->wp_waves == 8) hipLaunchKernelGGL((k_fill_v3<8, 3, true>), dim3(nv), dim3(8 * 64), pad, c->stream, c->st, c->jb);
-            else if (c->wp_waves == 4) hipLaunchKernelGGL((k_fill_v3<4, 6, true>), dim3(nv), dim3(4 * 64), pad, c->stream, c->st, c->jb);
-            else if (c->wp_waves == 3) hipLaunchKernelGGL((k_fill_v3<3, 8, true>), dim3(nv), dim3(3 * 64), pad, c->stream, c->st, c->jb);
-            else hipLaunchKernelGGL((k_fill_v3<9, 2, true>), dim3(nv), dim3(9 * 64), pad, c->stream, c->st, c->jb);
+            with_geometry(c, [&](auto NW, auto C) {
+                if constexpr (NW != 17 && !(NW == 9 && C == 4))
+                    hipLaunchKernelGGL((k_fill_v3<NW, C, true>), dim3(nv), dim3(NW * 64), pad, c->stream, c->st, c->jb);
+            });
         }
-        else if (c->wp_waves == 17) hipLaunchKernelGGL((k_fill_v3<17, 1, false>), grid, dim3(128), 0, c->stream, c->st, c->jb);
-        else if (c->wp_waves == 5) hipLaunchKernelGGL((k_fill_v3<5, 4, false>), grid, dim3(128), (size_t)c->fill_lds, c->stream, c->st, c->jb);
-        else if (c->wp_waves == 8) hipLaunchKernelGGL((k_fill_v3<8, 3, false>), grid, dim3(128), 0, c->stream, c->st, c->jb);
-        else if (c->wp_waves == 4) hipLaunchKernelGGL((k_fill_v3<4, 6, false>), grid, dim3(128), 0, c->stream, c->st, c->jb);
-        else if (c->wp_waves == 3) hipLaunchKernelGGL((k_fill_v3<3, 8, false>), grid, dim3(128), 0, c->stream, c->st, c->jb);
-        else if (c->B <= 1024 && c->wave_cols != 4) hipLaunchKernelGGL((k_fill_v3<9, 2, false>), grid, dim3(128), 0, c->stream, c->st, c->jb);
-        else hipLaunchKernelGGL((k_fill_v3<9, 4, false>), grid, dim3(128), 0, c->stream, c->st, c->jb);
+        else with_geometry(c, [&](auto NW, auto C) {
+            const size_t lds = NW == 5 ? (size_t)c->fill_lds : 0;               // ("fill_lds" is an experiment on the default fill alone)
+            hipLaunchKernelGGL((k_fill_v3<NW, C, false>), grid, dim3(128), lds, c->stream, c->st, c->jb);
+        });
         c->jb.stall_test = 0;
         if (c->jb.smax > 1 && c->jb.seg_rows > 0 && !c->jb.check_in_trace)
             hipLaunchKernelGGL(k_seg_check, dim3(njobs, c->jb.smax - 1), dim3(256), 0, c->stream, c->st, c->jb);
@@ -4646,12 +4725,10 @@ static int launch_fill(pwr_ctx *c, int njobs)
     c->jb.gate_v2 = c->fill_mode == 4 ? 1 : 0;
     if (c->fill_mode == 3) c->jb.v2_follows = 1;
     if (c->fill_mode == 3 || (c->fill_mode == 4 && c->jb.v2_follows)) {
-        if (c->wp_waves == 5) hipLaunchKernelGGL((k_fill_v2<5, 4>), dim3(njobs), dim3(5 * 64), 0, c->stream, c->st, c->jb);
-        else if (c->wp_waves == 8) hipLaunchKernelGGL((k_fill_v2<8, 3>), dim3(njobs), dim3(8 * 64), 0, c->stream, c->st, c->jb);
-        else if (c->wp_waves == 4) hipLaunchKernelGGL((k_fill_v2<4, 6>), dim3(njobs), dim3(4 * 64), 0, c->stream, c->st, c->jb);
-        else if (c->wp_waves == 3) hipLaunchKernelGGL((k_fill_v2<3, 8>), dim3(njobs), dim3(3 * 64), 0, c->stream, c->st, c->jb);
-        else if (c->B <= 1024 && c->wave_cols != 4) hipLaunchKernelGGL((k_fill_v2<9, 2>), dim3(njobs), dim3(9 * 64), 0, c->stream, c->st, c->jb);
-        else hipLaunchKernelGGL((k_fill_v2<9, 4>), dim3(njobs), dim3(9 * 64), 0, c->stream, c->st, c->jb);
+        with_geometry(c, [&](auto NW, auto C) {
+            if constexpr (NW != 17)                                             // (17 x 64 threads do not fit one work-group: settle_geometry, v2_follows)
+                hipLaunchKernelGGL((k_fill_v2<NW, C>), dim3(njobs), dim3(NW * 64), 0, c->stream, c->st, c->jb);
+        });
     } else if (c->fill_mode != 4) return PWR_ERR_ARG;
     HIPC(hipGetLastError());
     if (timed) { HIPC(hipEventRecord(e1, c->stream)); c->stats.fill_launches_timed += 1; }
@@ -4723,8 +4800,8 @@ static int enqueue_front(pwr_ctx *c)
     if ((rc = launch_fill(c, n))) return rc;
     if (c->jb.f64_follows) hipLaunchKernelGGL(k_fill64, dim3(n), dim3(F64_NT), 0, c->stream, c->st, c->jb);   // jobs the gather flagged wide
     if (c->par_trace) {
-        if (++c->trace_epoch >= (1u << 14)) { HIPC(hipMemsetAsync(c->jb.gtr, 0, (size_t)c->njobs * c->jb.trk * 8, c->stream)); c->trace_epoch = 1; }
-        c->jb.trace_tag = c->trace_epoch;
+        if (++c->trace_epoch >= (1 << 14)) { HIPC(hipMemsetAsync(c->jb.gtr, 0, (size_t)c->njobs * c->jb.trk * 8, c->stream)); c->trace_epoch = 1; }
+        c->jb.trace_tag = (unsigned)c->trace_epoch;
         c->jb.trace_blk = (c->par_trace == 2 && c->st.colcap < TB_MAXCOL) ? 1 : 0;
         c->jb.trace_prior = c->trace_prior;
         if (c->jb.trace_blk) hipLaunchKernelGGL(k_trace_blk, dim3(n, c->jb.trace_ny + (c->jb.check_in_trace ? c->jb.smax - 1 : 0)), dim3(TB_W * 64), 0, c->stream, c->st, c->jb);
@@ -4878,7 +4955,7 @@ static int realign_range(pwr_ctx *c, int k0, int n)
     return realign_positions(c, p0, pn);
 }
 
-extern "C" int pwr_realign_row(pwr_ctx *c, int k)
+static int realign_row(pwr_ctx *c, int k)
 {
     if (!c || k < 0 || k >= c->T) return PWR_ERR_ARG;
     int rc = ensure_device(c);
@@ -4886,7 +4963,7 @@ extern "C" int pwr_realign_row(pwr_ctx *c, int k)
     return realign_range(c, k, 1);
 }
 
-extern "C" int pwr_realign_rows(pwr_ctx *c, int k0, int n)
+static int realign_rows(pwr_ctx *c, int k0, int n)
 {
     if (!c || k0 < 0 || n < 0 || k0 > c->T || n > c->T - k0) return PWR_ERR_ARG;
     int rc = ensure_device(c);
@@ -4895,7 +4972,7 @@ extern "C" int pwr_realign_rows(pwr_ctx *c, int k0, int n)
     return realign_range(c, k0, n);
 }
 
-extern "C" int pwr_realign_round(pwr_ctx *c)
+static int realign_round(pwr_ctx *c)
 {
     if (!c) return PWR_ERR_ARG;
     int rc = ensure_device(c);
@@ -4914,7 +4991,7 @@ extern "C" int pwr_realign_round(pwr_ctx *c)
 // all-gather produces).  The collective is the caller's (torch.distributed / RCCL): this library links no communication
 // library.  The results are those of pwr_realign_rows(k0, n) on one GPU, bit for bit.
 // ---------------------------------------------------------------------------------------------
-extern "C" int pwr_split_begin(pwr_ctx *c, int k0, int n, int rank, int world)
+static int split_begin(pwr_ctx *c, int k0, int n, int rank, int world)
 {
     if (!c || k0 < 0 || n < 0 || k0 > c->T || n > c->T - k0 || world < 1 || rank < 0 || rank >= world) return PWR_ERR_ARG;
     int rc = ensure_device(c);
@@ -4926,7 +5003,7 @@ extern "C" int pwr_split_begin(pwr_ctx *c, int k0, int n, int rank, int world)
     return slab_init(c, c->split_k0, c->split_kend - c->split_k0);
 }
 
-extern "C" int pwr_split_slot_bytes(pwr_ctx *c, size_t *slot_bytes, int *slots_per_rank)
+static int split_slots(pwr_ctx *c, size_t *slot_bytes, int *slots_per_rank)
 {
     if (!c || !slot_bytes || !slots_per_rank) return PWR_ERR_ARG;
     int rc = ensure_device(c);
@@ -4936,7 +5013,7 @@ extern "C" int pwr_split_slot_bytes(pwr_ctx *c, size_t *slot_bytes, int *slots_p
     return PWR_OK;
 }
 
-extern "C" int pwr_split_stage(pwr_ctx *c, void *send_dev)
+static int split_stage(pwr_ctx *c, void *send_dev)
 {
     if (!c || !send_dev || !c->on_device) return PWR_ERR_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return PWR_ERR_DEVICE;
@@ -4948,7 +5025,7 @@ extern "C" int pwr_split_stage(pwr_ctx *c, void *send_dev)
     return PWR_OK;
 }
 
-extern "C" int pwr_split_commit(pwr_ctx *c, const void *recv_dev, int *rows_left)
+static int split_commit(pwr_ctx *c, const void *recv_dev, int *rows_left)
 {
     if (!c || !recv_dev || !rows_left || !c->on_device) return PWR_ERR_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return PWR_ERR_DEVICE;
@@ -4972,7 +5049,7 @@ extern "C" int pwr_split_commit(pwr_ctx *c, const void *recv_dev, int *rows_left
     return PWR_OK;
 }
 
-extern "C" int pwr_total_score(pwr_ctx *c, uint64_t *total)
+static int total_score(pwr_ctx *c, uint64_t *total)
 {
     if (!c || !total) return PWR_ERR_ARG;
     if (!c->on_device) {
@@ -5022,7 +5099,7 @@ extern "C" int pwr_dims(pwr_ctx *c, int *rows, int *width)
     return PWR_OK;
 }
 
-extern "C" int pwr_export_rows(pwr_ctx *c, unsigned char *buf, size_t cap)
+static int export_rows(pwr_ctx *c, unsigned char *buf, size_t cap)
 {
     static const char chars[6] = {'A', 'C', 'G', 'T', '-', ' '};              // PW:1558-1563
     if (!c || !buf) return PWR_ERR_ARG;
@@ -5056,7 +5133,7 @@ extern "C" int pwr_export_rows(pwr_ctx *c, unsigned char *buf, size_t cap)
 // '\n' -- is made on the device in stream order (so the calls that follow may change the state at once) and copied to
 // page-locked host memory on a second stream; pwr_snapshot_wait blocks until it is there.  The 1.8 GB the drop-in rewrites
 // after every improving round (PW:1741) leave the critical path this way (pwr_host.c hands the image to a writer thread).
-extern "C" int pwr_snapshot_begin(pwr_ctx *c, pwr_snapshot **out)
+static int snapshot_begin(pwr_ctx *c, pwr_snapshot **out)
 {
     if (!c || !out) return PWR_ERR_ARG;
     *out = nullptr;
@@ -5118,7 +5195,7 @@ extern "C" void pwr_snapshot_free(pwr_snapshot *sn)
     delete sn;
 }
 
-extern "C" int pwr_trim_ends(pwr_ctx *c)
+static int trim_ends(pwr_ctx *c)
 {
     if (!c) return PWR_ERR_ARG;
     if (!c->on_device) { host_trim(c); return PWR_OK; }
@@ -5131,101 +5208,33 @@ extern "C" int pwr_trim_ends(pwr_ctx *c)
 extern "C" int pwr_set_option(pwr_ctx *c, const char *key, long value)
 {
     if (!c || !key) return PWR_ERR_ARG;
-    // (capped: every work-group of a k_fill_v3 launch must be resident at once -- 9 of 128 threads per job -- and a
-    // window beyond what one CU-full of jobs survives is of no use anyway)
-    if (!strcmp(key, "window")) { if (value < 1 || value > 128 || c->on_device) return PWR_ERR_ARG; c->window = (int)value; return PWR_OK; }
-    if (!strcmp(key, "profile")) { if (value < 0 || value > 1000000) return PWR_ERR_ARG; c->profile = (int)value; return PWR_OK; }
-    if (!strcmp(key, "spec_len")) { if (value < 0 || value > 100000) return PWR_ERR_ARG; c->spec_len = (int)value; return PWR_OK; }
-    if (!strcmp(key, "fill")) { if (c->on_device || (value != 3 && value != 4)) return PWR_ERR_ARG; c->fill_mode = (int)value; return PWR_OK; }
-    if (!strcmp(key, "stall_test")) { if (value < 0 || value > 1000000) return PWR_ERR_ARG; c->stall_test = (int)value; return PWR_OK; }
-    if (!strcmp(key, "evcap")) { if (value < 0 || value > EVCAP) return PWR_ERR_ARG; c->evcap = (int)value; c->jb.evcap = (int)value; return PWR_OK; }
-    if (!strcmp(key, "force64")) { if (value != 0 && value != 1) return PWR_ERR_ARG; c->force64 = (int)value; c->jb.force64 = (int)value; return PWR_OK; }
-    if (!strcmp(key, "ptrace")) { if (value < 0 || value > 2) return PWR_ERR_ARG; c->par_trace = (int)value; return PWR_OK; }
-    if (!strcmp(key, "slack")) { if (c->on_device || value < 0) return PWR_ERR_ARG; c->cap_slack = (int)value; return PWR_OK; }
-    // (test hooks: where the launch counters behind the mailbox / hand-over tags stand, so that their wrap-around can be exercised)
-    if (!strcmp(key, "fill_epoch")) { if (value < 0 || value >= (1 << 15)) return PWR_ERR_ARG; c->fill_epoch = (unsigned)value; return PWR_OK; }
-    if (!strcmp(key, "trace_epoch")) { if (value < 0 || value >= (1 << 14)) return PWR_ERR_ARG; c->trace_epoch = (unsigned)value; return PWR_OK; }
-    if (!strcmp(key, "onewg")) { if (value != 0 && value != 1) return PWR_ERR_ARG; c->one_wg = (int)value; return PWR_OK; }
-    if (!strcmp(key, "fill_lds")) { if (value < 0 || value > 100000) return PWR_ERR_ARG; c->fill_lds = (int)value; return PWR_OK; }
-    if (!strcmp(key, "onewg_lds")) { if (value < 0 || value > 100000) return PWR_ERR_ARG; c->one_wg_lds = (int)value; return PWR_OK; }
-    if (!strcmp(key, "seg_rows")) { if (c->on_device || value < 0 || value > 1000000) return PWR_ERR_ARG; c->seg_rows = (int)value; return PWR_OK; }
-    if (!strcmp(key, "seg_align")) { if (c->on_device || (value != 16 && value != 32 && value != 64)) return PWR_ERR_ARG; c->seg_align = (int)value; return PWR_OK; }
-    if (!strcmp(key, "seg_max")) { if (c->on_device || value < 1 || value > SEG_MAX) return PWR_ERR_ARG; c->seg_max = (int)value; return PWR_OK; }
-    if (!strcmp(key, "seg_budget")) { if (value < 0 || value > 100000) return PWR_ERR_ARG; c->seg_budget = (int)value; c->jb.seg_budget = (int)value; return PWR_OK; }
-    if (!strcmp(key, "plan_slack")) { if (value < 0 || value > 1000000) return PWR_ERR_ARG; c->plan_slack = (int)value; c->jb.plan_slack = (int)value; return PWR_OK; }
-    if (!strcmp(key, "hard_rows")) { if (c->on_device || value < 0 || value > 2) return PWR_ERR_ARG; c->hard_rows = (int)value; return PWR_OK; }
-    if (!strcmp(key, "hard_up_pm")) { if (c->on_device || value < 1 || value > 100000) return PWR_ERR_ARG; c->hard_up_pm = (int)value; return PWR_OK; }
-    if (!strcmp(key, "hard_down_pm")) { if (c->on_device || value < 0 || value > 100000) return PWR_ERR_ARG; c->hard_down_pm = (int)value; return PWR_OK; }
-    if (!strcmp(key, "check_in_trace")) { if (value < 0 || value > 1) return PWR_ERR_ARG; c->check_in_trace = (int)value; return PWR_OK; }
-    if (!strcmp(key, "trace_prior")) { if (value < 0 || value > 1) return PWR_ERR_ARG; c->trace_prior = (int)value; return PWR_OK; }
-    if (!strcmp(key, "plan_len")) { if (value < 0 || value > 100000) return PWR_ERR_ARG; c->plan_len = (int)value; c->jb.plan_len = (int)value; return PWR_OK; }
-    if (!strcmp(key, "plan_gate_rel")) { if (value < 0 || value > 1) return PWR_ERR_ARG; c->plan_gate_rel = (int)value; c->jb.plan_gate_rel = (int)value; return PWR_OK; }
-    if (!strcmp(key, "spec_inorder")) { if (value < 0 || value > 64) return PWR_ERR_ARG; c->spec_inorder = (int)value; c->jb.spec_inorder = (int)value; return PWR_OK; }
-    if (!strcmp(key, "fail_stops")) { if (value < 0 || value > 1) return PWR_ERR_ARG; c->fail_stops = (int)value; c->jb.fail_stops = (int)value; return PWR_OK; }
-    if (!strcmp(key, "plan_evrate_x100")) { if (value < 0 || value > 100000000) return PWR_ERR_ARG; c->plan_evrate_x100 = (int)value; c->jb.plan_evrate_x100 = (int)value; return PWR_OK; }
-    if (!strcmp(key, "plan_ahead")) { if (value != 0 && value != 1) return PWR_ERR_ARG; c->plan_ahead = (int)value; c->jb.plan_ahead = (int)value; return PWR_OK; }
-    if (!strcmp(key, "seg_balance")) { if (value != 0 && value != 1) return PWR_ERR_ARG; c->seg_balance = (int)value; c->jb.seg_balance = (int)value; return PWR_OK; }
-    if (!strcmp(key, "seg_minrows")) { if (value < 16 || value > 100000) return PWR_ERR_ARG; c->seg_minrows = (int)value; c->jb.seg_minrows = (int)value; return PWR_OK; }
-    if (!strcmp(key, "src_start")) { if (c->on_device || value < 0 || value > 1) return PWR_ERR_ARG; c->src_start = (int)value; return PWR_OK; }
-    if (!strcmp(key, "warm_adapt")) { if (c->on_device || value < 0 || value > 1) return PWR_ERR_ARG; c->warm_adapt = (int)value; return PWR_OK; }
-    if (!strcmp(key, "warm_down_pm")) { if (c->on_device || value < 1 || value > 1000) return PWR_ERR_ARG; c->warm_down_pm = (int)value; return PWR_OK; }
-    if (!strcmp(key, "warm_up_pm")) { if (c->on_device || value < 1 || value > 10000) return PWR_ERR_ARG; c->warm_up_pm = (int)value; return PWR_OK; }
-    if (!strcmp(key, "warm_min_pct")) { if (c->on_device || value < 0 || value > 100000) return PWR_ERR_ARG; c->warm_min_pct = (int)value; return PWR_OK; }
-    if (!strcmp(key, "warm_pct")) { if (c->on_device || value < 0 || value > 100000) return PWR_ERR_ARG; c->warm_pct = (int)value; return PWR_OK; }
-    if (!strcmp(key, "wave_cols")) { if (c->on_device || (value != 0 && value != 4)) return PWR_ERR_ARG; c->wave_cols = (int)value; return PWR_OK; }
-    if (!strcmp(key, "waves")) { if (c->on_device || (value != 3 && value != 4 && value != 5 && value != 8 && value != 9 && value != 17)) return PWR_ERR_ARG; c->wp_waves = (int)value; return PWR_OK; }
-    return PWR_ERR_ARG;
+    const Option *o = find_option(key);
+    if (!o || value < o->lo || value > o->hi || (o->host_only && c->on_device)) return PWR_ERR_ARG;
+    if (o->nof && std::find(o->of, o->of + o->nof, (int)value) == o->of + o->nof) return PWR_ERR_ARG;
+    c->*o->field = (int)value;
+    if (o->mirror) c->jb.*o->mirror = (int)value;
+    return PWR_OK;
 }
 
 extern "C" int pwr_get_option(pwr_ctx *c, const char *key, long *value)
 {
     if (!c || !key || !value) return PWR_ERR_ARG;
-    if (!strcmp(key, "window")) *value = c->window;
-    else if (!strcmp(key, "profile")) *value = c->profile;
-    else if (!strcmp(key, "spec_len")) *value = c->spec_len;
-    else if (!strcmp(key, "fill")) *value = c->fill_mode;
-    else if (!strcmp(key, "ptrace")) *value = c->par_trace;
-    else if (!strcmp(key, "force64")) *value = c->force64;
-    else if (!strcmp(key, "slack")) *value = c->cap_slack;
-    else if (!strcmp(key, "waves")) *value = c->wp_waves;
-    else if (!strcmp(key, "onewg")) *value = c->one_wg;
-    else if (!strcmp(key, "seg_rows")) *value = c->seg_rows;
-    else if (!strcmp(key, "seg_max")) *value = c->seg_max;
-    else if (!strcmp(key, "seg_budget")) *value = c->seg_budget;
-    else if (!strcmp(key, "seg_minrows")) *value = c->seg_minrows;
-    else if (!strcmp(key, "seg_balance")) *value = c->seg_balance;
-    else if (!strcmp(key, "plan_ahead")) *value = c->plan_ahead;
-    else if (!strcmp(key, "plan_slack")) *value = c->plan_slack;
-    else if (!strcmp(key, "plan_evrate_x100")) *value = c->plan_evrate_x100;
-    else if (!strcmp(key, "fail_stops")) *value = c->fail_stops;
-    else if (!strcmp(key, "spec_inorder")) *value = c->spec_inorder;
-    else if (!strcmp(key, "plan_gate_rel")) *value = c->plan_gate_rel;
-    else if (!strcmp(key, "plan_len")) *value = c->plan_len;
-    else if (!strcmp(key, "check_in_trace")) *value = c->check_in_trace;
-    else if (!strcmp(key, "trace_prior")) *value = c->trace_prior;
-    else if (!strcmp(key, "hard_rows")) *value = c->hard_rows;
-    else if (!strcmp(key, "hard_up_pm")) *value = c->hard_up_pm;
-    else if (!strcmp(key, "hard_down_pm")) *value = c->hard_down_pm;
-    else if (!strcmp(key, "hard_marked") || !strcmp(key, "hard_fills") || !strcmp(key, "hard_refail")) {   // read-only counters of "hard_rows"
+    if (const Option *o = find_option(key)) { *value = c->*o->field; return PWR_OK; }
+    // the read-only keys: what the device header or the host's clocks say
+    if (!strcmp(key, "hard_marked") || !strcmp(key, "hard_fills") || !strcmp(key, "hard_refail")) {   // counters of "hard_rows"
         *value = 0;
         if (c->on_device) { Hdr h; int rc = read_hdr(c, &h); if (rc) return rc; *value = (long)(key[5] == 'm' ? h.hard_marked : key[5] == 'f' ? h.hard_fills : h.hard_refail); }
     }
-    else if (!strcmp(key, "evrate_x100")) {                                    // read-only: columns a commit opens / empties, running mean x 100
+    else if (!strcmp(key, "evrate_x100")) {                                    // columns a commit opens / empties, running mean x 100
         *value = 0;
         if (c->on_device) { Hdr h; int rc = read_hdr(c, &h); if (rc) return rc; *value = (long)(h.evrate * 100.0f); }
     }
-    else if (!strcmp(key, "warm_pct")) *value = c->warm_pct;
-    else if (!strcmp(key, "src_start")) *value = c->src_start;
-    else if (!strcmp(key, "warm_adapt")) *value = c->warm_adapt;
-    else if (!strcmp(key, "host_enqueue_us")) *value = (long)(c->host_enqueue_s * 1e6);   // read-only, since the context was made
+    else if (!strcmp(key, "host_enqueue_us")) *value = (long)(c->host_enqueue_s * 1e6);   // since the context was made
     else if (!strcmp(key, "host_wait_us")) *value = (long)(c->host_wait_s * 1e6);
     else if (!strcmp(key, "warm_now")) {                                      // percent of the bandwidth a warm-up covers right now
         if (!c->on_device) *value = c->warm_pct;
         else { Hdr h; int rc = read_hdr(c, &h); if (rc) return rc; *value = h.warm_step > 0 ? (long)(((long long)h.warm_cur * 100 + c->B / 2) / c->B) : c->warm_pct; }
     }
-    else if (!strcmp(key, "warm_min_pct")) *value = c->warm_min_pct;
-    else if (!strcmp(key, "warm_down_pm")) *value = c->warm_down_pm;
-    else if (!strcmp(key, "warm_up_pm")) *value = c->warm_up_pm;
     else return PWR_ERR_ARG;
     return PWR_OK;
 }
@@ -5280,7 +5289,7 @@ extern "C" int pwr_debug_last_job(pwr_ctx *c, int *L, int *entry, int *W, int *w
 
 // column ordinals of the bases of row k, left to right (the counterpart of the oracle's pwo_row_columns); returns the
 // number of bases or a negative error
-extern "C" int pwr_debug_row_columns(pwr_ctx *c, int k, int *out, int cap)
+static int debug_row_columns(pwr_ctx *c, int k, int *out, int cap)
 {
     if (!c || !c->on_device || k < 0 || k >= c->T || !out) return PWR_ERR_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return PWR_ERR_DEVICE;
@@ -5340,3 +5349,22 @@ extern "C" int pwr_debug_fill_clock(pwr_ctx *c, double *mhz, double *fill_us)
     if (fill_us) *fill_us = (double)m.rclk / 100.0;
     return PWR_OK;
 }
+
+// ---- the entries of the C ABI whose bodies can allocate on the host (vectors and threads over the whole text, the lists of
+// device buffers, the event pool): no exception leaves them (abi_guard.h) ----
+extern "C" int pwr_create(pwr_ctx **out, int rows, int width, const unsigned char *text, int bandwidth, int device)
+{
+    return abi_guard([&] { return create(out, rows, width, text, bandwidth, device); });
+}
+extern "C" int pwr_trim_ends(pwr_ctx *c) { return abi_guard([&] { return trim_ends(c); }); }
+extern "C" int pwr_realign_row(pwr_ctx *c, int k) { return abi_guard([&] { return realign_row(c, k); }); }
+extern "C" int pwr_realign_rows(pwr_ctx *c, int k0, int n) { return abi_guard([&] { return realign_rows(c, k0, n); }); }
+extern "C" int pwr_realign_round(pwr_ctx *c) { return abi_guard([&] { return realign_round(c); }); }
+extern "C" int pwr_split_begin(pwr_ctx *c, int k0, int n, int rank, int world) { return abi_guard([&] { return split_begin(c, k0, n, rank, world); }); }
+extern "C" int pwr_split_slot_bytes(pwr_ctx *c, size_t *slot_bytes, int *slots_per_rank) { return abi_guard([&] { return split_slots(c, slot_bytes, slots_per_rank); }); }
+extern "C" int pwr_split_stage(pwr_ctx *c, void *send_dev) { return abi_guard([&] { return split_stage(c, send_dev); }); }
+extern "C" int pwr_split_commit(pwr_ctx *c, const void *recv_dev, int *rows_left) { return abi_guard([&] { return split_commit(c, recv_dev, rows_left); }); }
+extern "C" int pwr_total_score(pwr_ctx *c, uint64_t *total) { return abi_guard([&] { return total_score(c, total); }); }
+extern "C" int pwr_export_rows(pwr_ctx *c, unsigned char *buf, size_t cap) { return abi_guard([&] { return export_rows(c, buf, cap); }); }
+extern "C" int pwr_snapshot_begin(pwr_ctx *c, pwr_snapshot **out) { return abi_guard([&] { return snapshot_begin(c, out); }); }
+extern "C" int pwr_debug_row_columns(pwr_ctx *c, int k, int *out, int cap) { return abi_guard([&] { return debug_row_columns(c, k, out, cap); }); }
