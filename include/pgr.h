@@ -325,6 +325,54 @@ void pgr_assignment_free(pgr_assignment *out);
  * [3] the distance and best kernels, [4] the downloads.  (Kept per process, not per call.) */
 int  pgr_last_assign_timing(double *ms5);
 
+/* ---- a labelling settled on the device: consensus and assignment iterated (pgr_settle_device.hip) ---- */
+/* The two calls above are the halves of one loop; this entry runs it on the device.  THE REFERENCE HAS NO COUNTERPART.  The
+ * result is defined by the composition of the public calls (resolution.consensus / assign / Assignment.labels are the Python
+ * names of the steps), everything an integer:
+ *   lab = labels; history = []; last = none; stop = MAX_ITER
+ *   for it in 0 .. max_iter - 1:
+ *       con = pgr_msa_consensus(lab, von, bis, maxcorrs_full, cutoff)
+ *       columns = the candidates at which every part of con has depth >= min_depth; none: stop = NO_COLUMN, break
+ *       a = pgr_msa_assign(con.consensus, columns)
+ *       new[r] = con.part_label[a.best[r]] where a.best[r] >= 0, a.compared[r] >= min_compared and (a.second[r] == -1 or
+ *                a.second_mismatches[r] - a.best_mismatches[r] >= min_margin), else -1; with hold, labels[r] -- the INITIAL
+ *                label -- wherever that is >= 0
+ *       changed = the rows with new != lab; history += (changed, con.parts, the number of columns); last = a
+ *       changed == 0: stop = CONVERGED, break;  no new[r] >= 0: stop = EMPTY, break (lab stays);  lab = new
+ * The candidates are con.selected (every column of the window with all_columns != 0, or maxcorrs_full = NULL) and are fixed for
+ * the call; which of them are compared changes with the depths.  The parts of an iteration are the labels that occur in lab
+ * then, ascending, as a fresh pgr_msa_consensus numbers them: a label no row holds any more is no part, constrains no column,
+ * and no row can join it (with hold the initial labels never die).  best and second are indices among the parts of the LAST
+ * iteration -- the one whose assignment made the labels returned; with EMPTY the one that emptied the labelling --, part_label
+ * [parts] their labels, columns[ncolumns] its compared columns.  NO_COLUMN in iteration 0 has no last iteration: parts,
+ * ncolumns and iterations are 0 and every array but labels is NULL, the three histories included. */
+#define PGR_ST_CONVERGED 0       /* an iteration moved no row */
+#define PGR_ST_MAX_ITER 1        /* max_iter iterations, the last of which still moved rows */
+#define PGR_ST_EMPTY 2           /* an iteration left no row with a label: the labelling before it is returned */
+#define PGR_ST_NO_COLUMN 3       /* no candidate column at which every part has depth >= min_depth */
+
+typedef struct {
+    int rows, iterations, stop, parts;        /* iterations = entries of the history; stop: PGR_ST_*; parts of the last iteration */
+    int *part_label;                          /* [parts] */
+    int *labels;                              /* [rows] the settled labelling */
+    int *changed, *parts_at, *ncolumns_at;    /* [iterations] rows moved, parts, compared columns of every iteration */
+    int ncolumns; int *columns;               /* the compared columns of the last iteration: absolute, ascending */
+    int *compared, *best, *second, *best_mismatches, *second_mismatches;   /* [rows] as pgr_assignment, of the last iteration */
+} pgr_settlement;
+
+/* The rows' bit planes over the candidates stay on the device for the whole call: 32 * ceil(candidates / 64) * rows bytes, and
+ * 4 * rows * parts bytes of mismatches; PWR_ERR_NOMEM if the device refuses (there are no ranges).  Argument errors as
+ * pgr_msa_consensus (PWR_ERR_ARG: a null pointer, a label below -1, von > bis, an end outside the text, no label >= 0;
+ * PWR_ERR_RANGE: a label >= PGR_MAX_ROWS) and PWR_ERR_ARG for max_iter < 1, min_depth < 1, min_compared < 0, min_margin < 0 --
+ * all refused before the device is touched.  *out is zeroed first and holds malloc'ed arrays (empty after a failure): release
+ * them with pgr_settlement_free.  Sums of integers only: no result depends on the order of the atomics. */
+int  pgr_msa_settle(pgr_msa *h, const int *labels, int von, int bis, const double *maxcorrs_full /* width*5 or NULL */, double cutoff,
+                    int min_depth, int all_columns, int min_compared, int min_margin, int hold, int max_iter, pgr_settlement *out);
+void pgr_settlement_free(pgr_settlement *out);
+/* Duration of the last pgr_msa_settle, ms: [0] all, [1] checks, candidates, allocation and upload, [2] the planes kernel,
+ * [3] the iterations in total, [4] the downloads.  (Kept per process, not per call.) */
+int  pgr_last_settle_timing(double *ms5);
+
 #ifdef __cplusplus
 }
 #endif

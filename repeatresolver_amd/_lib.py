@@ -45,7 +45,7 @@ PGR_EXPORTS = ["pgr_refine", "pgr_free", "pgr_last_timing", "pgr_read_window", "
                "pgr_last_kmeans_timing", "pgr_kmeans_reassign", "pgr_msa_open", "pgr_msa_close", "pgr_msa_window", "pgr_msa_resolve",
                "pgr_resolution_free", "pgr_last_resolve_timing", "pgr_connect", "pgr_connection_free", "pgr_msa_consensus",
                "pgr_consensus_free", "pgr_last_consensus_timing", "pgr_resolvability", "pgr_msa_assign", "pgr_assignment_free",
-               "pgr_last_assign_timing"]
+               "pgr_last_assign_timing", "pgr_msa_settle", "pgr_settlement_free", "pgr_last_settle_timing"]
 
 # constants of include/pgr.h that tests and scripts cite (pgr_cons_device.hip)
 PGR_MAX_ROWS = 30000
@@ -55,6 +55,9 @@ PGR_CS_SCRATCH_INTS = 1 << 25  # count entries on the device at a time: a wider 
 # (pgr_assign_device.hip)
 PGR_AS_SCRATCH_BYTES = 64 << 20  # planes and mismatch matrix of one range of rows: more rows go through in several ranges
 PGR_AS_TILE = 8               # parts per work-group of k_as_dist
+# (pgr_settle_device.hip) pgr_settlement.stop
+PGR_ST_CONVERGED, PGR_ST_MAX_ITER, PGR_ST_EMPTY, PGR_ST_NO_COLUMN = 0, 1, 2, 3
+PGR_ST_NAMES = ("CONVERGED", "MAX_ITER", "EMPTY", "NO_COLUMN")
 
 
 class PgrWindow(ctypes.Structure):
@@ -122,6 +125,15 @@ class PgrAssignment(ctypes.Structure):
                 ("best", ctypes.POINTER(ctypes.c_int)), ("second", ctypes.POINTER(ctypes.c_int)),
                 ("best_mismatches", ctypes.POINTER(ctypes.c_int)), ("second_mismatches", ctypes.POINTER(ctypes.c_int)),
                 ("mismatches", ctypes.POINTER(ctypes.c_int))]
+
+
+class PgrSettlement(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_int), ("iterations", ctypes.c_int), ("stop", ctypes.c_int), ("parts", ctypes.c_int),
+                ("part_label", ctypes.POINTER(ctypes.c_int)), ("labels", ctypes.POINTER(ctypes.c_int)),
+                ("changed", ctypes.POINTER(ctypes.c_int)), ("parts_at", ctypes.POINTER(ctypes.c_int)),
+                ("ncolumns_at", ctypes.POINTER(ctypes.c_int)), ("ncolumns", ctypes.c_int), ("columns", ctypes.POINTER(ctypes.c_int)),
+                ("compared", ctypes.POINTER(ctypes.c_int)), ("best", ctypes.POINTER(ctypes.c_int)), ("second", ctypes.POINTER(ctypes.c_int)),
+                ("best_mismatches", ctypes.POINTER(ctypes.c_int)), ("second_mismatches", ctypes.POINTER(ctypes.c_int))]
 
 
 _lib = None
@@ -328,5 +340,11 @@ def load():
     lib.pgr_assignment_free.argtypes = [ctypes.POINTER(PgrAssignment)]
     lib.pgr_last_assign_timing.restype = ci
     lib.pgr_last_assign_timing.argtypes = [pd]
+    lib.pgr_msa_settle.restype = ci
+    lib.pgr_msa_settle.argtypes = [vp, pi, ci, ci, pd, ctypes.c_double, ci, ci, ci, ci, ci, ci, ctypes.POINTER(PgrSettlement)]
+    lib.pgr_settlement_free.restype = None
+    lib.pgr_settlement_free.argtypes = [ctypes.POINTER(PgrSettlement)]
+    lib.pgr_last_settle_timing.restype = ci
+    lib.pgr_last_settle_timing.argtypes = [pd]
     _lib = lib
     return lib

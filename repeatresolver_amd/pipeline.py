@@ -114,10 +114,12 @@ def clustered(rows, von=None, bis=None, cov: int = 30, cutoff: float = 0.0, devi
     return sub, kmeans_subdivide(rows, refined, sub, von, bis, cov, device)
 
 
-def _resolved(rows, parts, coverage, cov, cutoff, device, copies, recruit=None):
+def _resolved(rows, parts, coverage, cov, cutoff, device, copies, recruit=None, settle=None):
     from .max_correlation import max_correlations
     from .resolution import assign, connect, consensus, open_msa, resolve
+    from .resolution import settle as settle_labels
     from .window import window_boundaries
+    assert not (recruit and settle)                                    # `assigned` or `settled`, one of them: each has its own return below
     sites = window_boundaries(rows, coverage, parts)
     mc = max_correlations(rows, cov, device)
     with open_msa(rows, device) as msa:
@@ -125,7 +127,12 @@ def _resolved(rows, parts, coverage, cov, cutoff, device, copies, recruit=None):
         cons = [consensus(msa, w.kmeans_labels, w.von, w.bis, mc, w.cutoff) if w.kept_rows > 0 else None
                 for w in windows] if copies else None
         assignments = [None if c is None else assign(msa, c) for c in cons] if recruit else None
+        settlements = [settle_labels(msa, w.kmeans_labels, w.von, w.bis, mc, w.cutoff, **settle) if w.kept_rows > 0 else None
+                       for w in windows] if settle else None
     con = connect([w.kmeans_labels for w in windows]) if len(windows) > 1 else None
+    if settle:
+        settled_labels = [w.kmeans_labels.copy() if s is None else s.labels for w, s in zip(windows, settlements)]
+        return sites, windows, con, cons, settlements, connect(settled_labels) if len(windows) > 1 else None
     if not recruit:
         return sites, windows, con, cons
     recruited = [w.kmeans_labels.copy() if a is None else a.labels(*recruit, keep=w.kmeans_labels) for w, a in zip(windows, assignments)]
@@ -163,3 +170,18 @@ def assigned(rows, parts: int = 6, coverage: float = 0.90, cov: int = 30, cutoff
       * the resolution.Connection of the recruited labellings (None for a single window).
     The two thresholds depend on the read error rate and the number of selected columns: they have no default."""
     return _resolved(rows, parts, coverage, cov, cutoff, device, True, (min_compared, min_margin))
+
+
+def settled(rows, parts: int = 6, coverage: float = 0.90, cov: int = 30, cutoff: float = 0.0, device: int = 0, *, min_compared,
+            min_margin, max_iter, hold: bool = True):
+    """resolved_copies, and every window's k-means labelling settled: `assigned` makes one pass from the copies to the reads and
+    the recruited rows never feed back into the consensus they were judged against; here the loop runs until nothing moves
+    (resolution.settle, on the device, from the same device copy of the MSA: the window's k-means labels over [w.von, w.bis],
+    the selected columns being those over w.cutoff).  Returns resolved_copies' four values and
+      * a list with one resolution.Settlement per window (None for a window that keeps no row),
+      * the resolution.Connection of the settled labellings (None for a single window; a window without a Settlement stands
+        there with its k-means labelling).
+    hold (the default here): the rows of the k-means labelling keep their label, as in `assigned`; with max_iter = 1 the settled
+    labellings are `assigned`'s recruited ones.  The thresholds and max_iter have no default."""
+    return _resolved(rows, parts, coverage, cov, cutoff, device, True,
+                     settle=dict(min_compared=min_compared, min_margin=min_margin, max_iter=max_iter, hold=hold))

@@ -329,6 +329,71 @@ def last_assign_timing():
     return {"all_ms": t[0], "prepare_ms": t[1], "planes_ms": t[2], "dist_best_ms": t[3], "download_ms": t[4]}
 
 
+@dataclass
+class Settlement:
+    """pgr_settlement (include/pgr.h): a labelling settled by iterating consensus, assign and Assignment.labels on the device.
+    The per-row arrays, part_label and columns are those of the last iteration -- the assignment the labels were made from (with
+    stop == "EMPTY": the one that emptied the labelling) --, None when there was none ("NO_COLUMN" in iteration 0)."""
+    labels: np.ndarray           # [rows] int32 the settled labelling
+    stop: str                    # "CONVERGED", "MAX_ITER", "EMPTY" or "NO_COLUMN"
+    iterations: int              # entries of the three histories
+    changed: np.ndarray          # [iterations] int32 rows whose label moved
+    parts_at: np.ndarray         # [iterations] the parts (labels that occur) the iteration started from
+    ncolumns_at: np.ndarray      # [iterations] its compared columns
+    part_label: object           # [parts] int32 the label of every part index of the last iteration
+    columns: object              # int32 the compared columns of the last iteration, absolute, ascending
+    compared: object             # [rows] int32, as Assignment
+    best: object
+    second: object
+    best_mismatches: object
+    second_mismatches: object
+
+
+def settle(msa: Msa, labels, von=None, bis=None, maxcorrs=None, cutoff: float = 1.0, *, min_compared, min_margin, max_iter,
+           min_depth: int = 1, all_columns: bool = False, hold: bool = False) -> Settlement:
+    """consensus(msa, lab, von, bis, maxcorrs, cutoff), assign(msa, con, min_depth, all_columns) and
+    a.labels(min_compared, min_margin, keep=labels if hold else None) iterated from lab = labels until no row moves
+    ("CONVERGED"), for max_iter iterations ("MAX_ITER"), until an iteration labels no row ("EMPTY": the labelling before it is
+    returned) or no column is left at which every part has the depth ("NO_COLUMN"), on the device (pgr_settle_device.hip): the
+    rows' bit planes stay resident and nothing but one small record per iteration crosses the bus.  A label that no row holds any
+    more is no part from then on; with hold the rows labelled at the start keep their label throughout.  The thresholds and
+    max_iter have no default, as in Assignment.labels."""
+    lib = _lib.load()
+    if (von is None) != (bis is None):
+        raise ValueError("von and bis go together")
+    lab = _labels(msa, labels)
+    mc = None
+    if maxcorrs is not None:
+        mc = np.ascontiguousarray(maxcorrs, dtype=np.float64)
+        if mc.shape != (msa.width * 5,):
+            raise ValueError("maxcorrs must hold width * 5 values")
+    out = _lib.PgrSettlement()
+    pi = ctypes.POINTER(ctypes.c_int)
+    _check(lib, lib.pgr_msa_settle(msa.handle, lab.ctypes.data_as(pi), -1 if von is None else von, -1 if bis is None else bis,
+                                   None if mc is None else mc.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), cutoff, min_depth,
+                                   1 if all_columns else 0, min_compared, min_margin, 1 if hold else 0, max_iter, ctypes.byref(out)))
+    try:
+        T, n = out.rows, out.iterations
+        per_row = [_copy(getattr(out, name), (T,), np.int32) if getattr(out, name) else None
+                   for name in ("compared", "best", "second", "best_mismatches", "second_mismatches")]
+        return Settlement(labels=_copy(out.labels, (T,), np.int32), stop=_lib.PGR_ST_NAMES[out.stop], iterations=n,
+                          changed=_copy(out.changed, (n,), np.int32) if n else np.zeros(0, np.int32),
+                          parts_at=_copy(out.parts_at, (n,), np.int32) if n else np.zeros(0, np.int32),
+                          ncolumns_at=_copy(out.ncolumns_at, (n,), np.int32) if n else np.zeros(0, np.int32),
+                          part_label=_copy(out.part_label, (out.parts,), np.int32) if out.part_label else None,
+                          columns=_copy(out.columns, (out.ncolumns,), np.int32) if out.columns else None,
+                          compared=per_row[0], best=per_row[1], second=per_row[2], best_mismatches=per_row[3], second_mismatches=per_row[4])
+    finally:
+        lib.pgr_settlement_free(ctypes.byref(out))
+
+
+def last_settle_timing():
+    lib = _lib.load()
+    t = (ctypes.c_double * 5)()
+    lib.pgr_last_settle_timing(t)
+    return {"all_ms": t[0], "prepare_ms": t[1], "planes_ms": t[2], "iterations_ms": t[3], "download_ms": t[4]}
+
+
 def write_copies(path, consensus: Consensus, name: str):
     """One FASTA record per part, `>name_<von>_<bis>_copy<label> rows=<n>` and the sequence on one line.  The format is this
     project's own: the reference writes no consensus."""
