@@ -35,7 +35,16 @@ void pia_destroy(pia_ctx *ctx);
  * offsets.  Out: align[off[j] + x] = template position of base x of read j, or -1 when the base is placed between two
  * template bases (IA:420-446); dist[j] = the edit distance Row[entry] (IA:352: AlignmentError = dist / length). */
 int pia_align(pia_ctx *ctx, int nreads, const char *bases, const long long *off, int *align, int *dist);
-/* DP cells filled so far (read length x template length per read) and the summed duration of the fill kernel in ms. */
+/* Reads from either strand.  rc(r)[x] = comp(r[L-1-x]), a<->t, c<->g, the letter's case kept.  With d_f and d_r the dist
+ * that pia_align gives for read j and for rc(read j): strand[j] = 1 iff d_r < d_f (a tie goes to the forward strand, an empty
+ * read is forward), dist[j] = min(d_f, d_r), dist_other[j] = the distance of the orientation not taken, and
+ * align[off[j] + x] = the template position of base x of the turned read -- align and dist are exactly what pia_align
+ * returns for the output of pia_turn.  Arguments and input are refused as pia_align refuses them.  On the device pass 1 runs
+ * both orientations of every read from the one copy of the bases (a job carries its strand), pass 2 only the one taken. */
+int pia_align_strands(pia_ctx *ctx, int nreads, const char *bases, const long long *off, int *align, int *dist,
+                      int *dist_other, unsigned char *strand);
+/* DP cells filled so far (read length x template length per read; pia_align_strands counts both orientations of pass 1, twice
+ * that) and the summed duration of the fill kernel in ms. */
 int pia_get_stats(pia_ctx *ctx, unsigned long long *cells, double *fill_ms);
 /* "mem_budget": bytes of device memory for the stored direction bits of one batch of reads (0 = the default: 22 GB, or
  * less when the card has less to spare -- three quarters of the free memory over the four buffers in flight; an allocation
@@ -47,6 +56,9 @@ int pia_set_option(pia_ctx *ctx, const char *key, long long value);
 int pia_get_timing(pia_ctx *ctx, double *ms6);
 
 /* ---- host side, plain C (pia_host.c) ---- */
+/* The reads as pia_align_strands aligned them, no GPU: out (same offsets as bases) = read j where strand[j] == 0,
+ * rc(read j) where strand[j] == 1.  A byte outside acgtACGT -> PWR_ERR_INPUT. */
+int pia_turn(int nreads, const char *bases, const long long *off, const unsigned char *strand, char *out);
 /* ReadingTemplate (IA:214-262): every line that does not start with '>' contributes its aAcCgGtT, lower-cased. */
 int pia_read_template(const char *path, char **templ, int *len);
 /* ReadCounter / Offsetter / ReadingFasta (IA:66-213): records start at '>' lines; *bases and *off are malloc'ed. */
@@ -59,6 +71,11 @@ int pia_build_msa(const char *msa_path, const char *class_path, int nreads, cons
  * the process exit code. */
 int pia_run_files(const char *templ_path, const char *reads_path, const char *msa_path, const char *class_path,
                   double cutoff, int cutoff_given, int device, FILE *log);
+/* The same with reads from either strand (`-b <strandfile>` of the drop-in): strand_path gets one line per record of the
+ * input, '+' or '-', the records the cut-off turns away included; the MSA and the class file are those of pia_run_files for
+ * the turned records; stdout is the same.  strand_path == NULL: pia_run_files. */
+int pia_run_files_strands(const char *templ_path, const char *reads_path, const char *msa_path, const char *class_path,
+                          const char *strand_path, double cutoff, int cutoff_given, int device, FILE *log);
 
 #ifdef __cplusplus
 }

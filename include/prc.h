@@ -43,7 +43,20 @@ int prc_occurrences(prc_ctx *ctx, int nreads, const char *bases, const long long
  * prc_free).  (RC:1053-1079 applies it to a different buffer for the last record of a file: prc_read_fasta.) */
 int prc_cut(prc_ctx *ctx, int nreads, const char *bases, const long long *off, int parts, int overlap, double error_cutoff,
             int *ncut, int **cuts);
-/* DP cells the reference fills for the calls so far (piece length x read length per query) and the summed kernel time, ms. */
+/* Reads from either strand.  rc(r)[x] = comp(r[L-1-x]), a<->t, c<->g.  prc_occurrences of every read and of its reverse
+ * complement from one copy of the bases (a job carries its strand): job k = (j * 2 + s) * nq + q is read j, strand s
+ * (1: rc(read j)), query q, and its positions are in the coordinates of that orientation.  pos_off holds nreads * 2 * nq + 1
+ * entries. */
+int prc_occurrences_strands(prc_ctx *ctx, int nreads, const char *bases, const long long *off, int parts, int overlap,
+                            double error_cutoff, long long *pos_off, int **pos);
+/* With F = prc_cut(read) and R = prc_cut(rc(read)): the read's cut points are the ascending union of F and
+ * {readlen - c : c in R}, each value once (prc_merge_cuts) -- cutting rc(read) at c is cutting read at readlen - c, so a
+ * reverse read is cut where its mirror image would be, and a read holding copies in both orientations is cut at both.
+ * nfwd[j] = |F|, nrev[j] = |R|.  No strand is decided here and nothing is turned: that is pia_align_strands' part. */
+int prc_cut_strands(prc_ctx *ctx, int nreads, const char *bases, const long long *off, int parts, int overlap,
+                    double error_cutoff, int *ncut, int **cuts, int *nfwd, int *nrev);
+/* DP cells the reference fills for the calls so far (piece length x read length per query; the _strands entries count both
+ * orientations) and the summed kernel time, ms. */
 int prc_get_stats(prc_ctx *ctx, unsigned long long *cells, double *kernel_ms);
 void prc_free(void *p);
 
@@ -66,6 +79,9 @@ int prc_scan_runs(const int *run, int nruns, int len1, int *pos);
  * piece parts-1 in the reference's order (posL ignored when parts == 1).  Writes the cut points to cuts (room for
  * 3 * n0 + 2 * nL + 1) and returns their number. */
 int prc_select_cuts(int parts, int len, int templ_len, int readlen, const int *pos0, int n0, const int *posL, int nL, int *cuts);
+/* The merge of prc_cut_strands for one read: fwd[0 .. nf) cut points of the read, rev[0 .. nr) of its reverse complement; out
+ * (room nf + nr) gets the ascending union of fwd and {readlen - c}, each value once.  Returns their number. */
+int prc_merge_cuts(int readlen, int nf, const int *fwd, int nr, const int *rev, int *out);
 /* OutputOfCuts (RC:887-913) for nrec records: ">\n", the bases with "\n>\n" before each cut point, "\n".  ncut[i] cut points
  * of record i, concatenated in cuts. */
 int prc_write_seq(const char *path, int nrec, const char *bases, const long long *off, const int *ncut, const int *cuts);
@@ -75,6 +91,10 @@ int prc_write_info(const char *path, int nrec, const int *ncut);
  * returns the process exit code.  (The caller prints the two default output names first, RC:972-973.) */
 int prc_run_files(const char *templ_path, const char *reads_path, const char *seq_path, const char *info_path, int parts,
                   int overlap, double error_cutoff, int wiggleroom, int device, FILE *log);
+/* The same with `-b 1` of the drop-in: both_strands != 0 uses prc_cut_strands where prc_run_files uses prc_cut; everything
+ * else, the last-record buffer included, stays.  The pieces are written in the read's own orientation and order. */
+int prc_run_files_strands(const char *templ_path, const char *reads_path, const char *seq_path, const char *info_path, int parts,
+                          int overlap, double error_cutoff, int wiggleroom, int both_strands, int device, FILE *log);
 
 #ifdef __cplusplus
 }

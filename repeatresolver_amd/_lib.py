@@ -27,12 +27,12 @@ EXPORTS = ["pwr_create", "pwr_destroy", "pwr_trim_ends", "pwr_realign_row", "pwr
 
 # every symbol include/pia.h declares (the InitialAligner)
 PIA_EXPORTS = ["pia_create", "pia_destroy", "pia_align", "pia_get_stats", "pia_set_option", "pia_get_timing", "pia_read_template", "pia_read_fasta",
-               "pia_build_msa", "pia_run_files"]
+               "pia_build_msa", "pia_run_files", "pia_align_strands", "pia_turn", "pia_run_files_strands"]
 
 # every symbol include/prc.h declares (the ReadCutter, the pipeline's first tool)
 PRC_EXPORTS = ["prc_create", "prc_destroy", "prc_occurrences", "prc_cut", "prc_get_stats", "prc_free", "prc_read_template",
                "prc_read_fasta", "prc_scan_dense", "prc_scan_runs", "prc_select_cuts", "prc_write_seq", "prc_write_info",
-               "prc_run_files"]
+               "prc_run_files", "prc_occurrences_strands", "prc_cut_strands", "prc_merge_cuts", "prc_run_files_strands"]
 
 # every symbol include/pmc.h declares (MaxCorrelation)
 PMC_EXPORTS = ["pmc_maxcorrs", "pmc_last_timing", "pmc_read_msa", "pmc_write", "pmc_run_file"]
@@ -215,6 +215,11 @@ def load():
     lib.pia_destroy.argtypes = [vp]
     lib.pia_align.restype = ci
     lib.pia_align.argtypes = [vp, ci, ctypes.c_char_p, ctypes.POINTER(ll), ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    lib.pia_align_strands.restype = ci
+    lib.pia_align_strands.argtypes = [vp, ci, ctypes.c_char_p, ctypes.POINTER(ll), ctypes.POINTER(ci), ctypes.POINTER(ci),
+                                      ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_ubyte)]
+    lib.pia_turn.restype = ci
+    lib.pia_turn.argtypes = [ci, ctypes.c_char_p, ctypes.POINTER(ll), ctypes.POINTER(ctypes.c_ubyte), ctypes.c_char_p]
     lib.pia_get_stats.restype = ci
     lib.pia_get_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double)]
     lib.pia_set_option.restype = ci
@@ -245,6 +250,12 @@ def load():
     lib.prc_occurrences.argtypes = [vp, ci, cp, pll, ci, ci, ctypes.c_double, pll, ctypes.POINTER(vp)]
     lib.prc_cut.restype = ci
     lib.prc_cut.argtypes = [vp, ci, cp, pll, ci, ci, ctypes.c_double, pi, ctypes.POINTER(vp)]
+    lib.prc_occurrences_strands.restype = ci
+    lib.prc_occurrences_strands.argtypes = lib.prc_occurrences.argtypes
+    lib.prc_cut_strands.restype = ci
+    lib.prc_cut_strands.argtypes = [vp, ci, cp, pll, ci, ci, ctypes.c_double, pi, ctypes.POINTER(vp), pi, pi]
+    lib.prc_merge_cuts.restype = ci
+    lib.prc_merge_cuts.argtypes = [ci, ci, pi, ci, pi, pi]
     lib.prc_get_stats.restype = ci
     lib.prc_get_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double)]
     lib.prc_free.restype = None

@@ -19,6 +19,13 @@
 // the traceback from there cannot leave the diagonal band of half-width `dist` around the entry's diagonal (each step off the
 // diagonal costs one), so pass 2 repeats the rows and stores two bits per cell for that band only -- a tenth of the full
 // matrices at sequencing error rates -- and the same wave then walks the traceback (IA:347-446) through what it has stored.
+//
+// Both strands (pia_align_strands): a job carries its strand.  Base x of rc(read) is the complement of read[L1-1-x], and with
+// the codes a c g t -> 0 1 3 2 the complement is code ^ 2, so a reverse job differs from a forward one only where the kernel
+// loads bases, the 64-step chunk load: it reads the chunk from the read's far end and flips bit 1.  Pass 1 runs both
+// orientations of every read over the one uploaded copy of the bases, the host keeps the nearer one (ties: forward), and pass
+// 2 runs for that orientation alone; x everywhere below is the base's index in the orientation the job aligns.  The kernels
+// that look at a job's strand are instances of their own (BOTH): pia_align runs the ones that do not, the code it always ran.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -42,8 +49,13 @@ struct IaRead {
     long long coff;                 // offset (uint2) of its band of direction bits, pass 2
     int L1;
     int dist, entry;                // pass 1: Row[entry] and the entry column (IA:333-345); dist = -1: traceback left the band
-    int nl;                         // lanes stored per row (pass 2)
+    int nl;                         // lanes stored per row (pass 2); | IA_REVERSE: the strand flag, see below
 };
+// The strand flag of a job of pia_align_strands: it aligns rc(read), read from the same bases backwards.  It is a bit of nl
+// (which stays below 2 * PIA_MAX_READ / 32 + 3) and only the BOTH kernels know it, so a job stays 32 bytes and the kernels of
+// pia_align are, struct and code, the ones they were.
+#define IA_REVERSE (1 << 30)
+static_assert(sizeof(IaRead) == 32, "a job is 32 bytes");
 
 // The stored band of row x are the columns [c - dist, c + dist] around the entry's diagonal c = entry - (L1 - 1 - x), widened
 // to whole lanes (32 * WPL columns each): first stored lane of row x
@@ -101,12 +113,15 @@ __device__ __forceinline__ void wave_trace(const IaRead &rd, IaRead *rdp, const 
     for (int i = x - lane; i >= 0; i -= 64) al[i] = -1;               // IA:389-394
 }
 
-template <int WPL, bool STORE>
+template <int WPL, bool STORE, bool BOTH>
 __global__ __launch_bounds__(64) void k_ia_bits(const uint32_t *__restrict__ tplanes, int L2, const char *__restrict__ bases,
                                                 IaRead *reads, const int *__restrict__ order, uint2 *__restrict__ codes, int *__restrict__ align)
 {
     IaRead *rdp = &reads[order[blockIdx.x]];
-    const IaRead rd = *rdp;
+    IaRead job = *rdp;
+    const int strand = BOTH ? (job.nl & IA_REVERSE) != 0 : 0;
+    if (BOTH) job.nl &= ~IA_REVERSE;
+    const IaRead rd = job;
     const int L1 = rd.L1, lane = threadIdx.x;
     if (L1 <= 0) { if (!STORE && lane == 0) { rdp->dist = 0; rdp->entry = L2 - 1; } return; }
     constexpr int NW = 64 * WPL;
@@ -122,7 +137,10 @@ __global__ __launch_bounds__(64) void k_ia_bits(const uint32_t *__restrict__ tpl
     int chunk = 0;
     const int steps = L1 + lastlane;
     for (int tau = 0; tau < steps; ++tau) {
-        if ((tau & 63) == 0) { const int i = tau + lane; chunk = i < L1 ? (read[i] >> 1) & 3 : 0; }     // a c g t -> 0 1 3 2
+        if ((tau & 63) == 0) {                     // a c g t -> 0 1 3 2; the one place bases are loaded: a reverse job takes them
+            const int i = tau + lane;             // from the far end, complemented (code ^ 2)
+            chunk = i < L1 ? ((read[strand ? L1 - 1 - i : i] >> 1) & 3) ^ (strand << 1) : 0;
+        }
         int m = __shfl_up(msg, 1);
         const int c0 = __builtin_amdgcn_readlane(chunk, tau & 63);
         if (lane == 0) m = c0 | 4;                // E(x,-1) - E(x-1,-1) = +1 (IA:301)
@@ -287,14 +305,15 @@ extern "C" int pia_get_timing(pia_ctx *c, double *ms6)
 }
 
 template <int WPL>
-static void launch_bits(pia_ctx *c, bool store, int n, const char *d_bases, IaRead *d_reads, const int *d_order, uint2 *d_codes, int *d_align, hipStream_t st)
+static void launch_bits(pia_ctx *c, bool store, bool both, int n, const char *d_bases, IaRead *d_reads, const int *d_order, uint2 *d_codes, int *d_align, hipStream_t st)
 {
     if (c->WPL == WPL) {
-        if (store) hipLaunchKernelGGL((k_ia_bits<WPL, true>), dim3(n), dim3(64), 0, st, c->d_planes, c->L2, d_bases, d_reads, d_order, d_codes, d_align);
-        else hipLaunchKernelGGL((k_ia_bits<WPL, false>), dim3(n), dim3(64), 0, st, c->d_planes, c->L2, d_bases, d_reads, d_order, d_codes, d_align);
+        auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(n), dim3(64), 0, st, c->d_planes, c->L2, d_bases, d_reads, d_order, d_codes, d_align); };
+        if (store) { if (both) go(k_ia_bits<WPL, true, true>); else go(k_ia_bits<WPL, true, false>); }
+        else { if (both) go(k_ia_bits<WPL, false, true>); else go(k_ia_bits<WPL, false, false>); }
         return;
     }
-    if constexpr (WPL < IA_MAXWPL) launch_bits<WPL + 1>(c, store, n, d_bases, d_reads, d_order, d_codes, d_align, st);
+    if constexpr (WPL < IA_MAXWPL) launch_bits<WPL + 1>(c, store, both, n, d_bases, d_reads, d_order, d_codes, d_align, st);
 }
 
 struct DevBufs {                    // freed on every way out of pia_align
@@ -310,9 +329,13 @@ struct DevBufs {                    // freed on every way out of pia_align
     }
 };
 
-static int align_reads(pia_ctx *c, int nreads, const char *bases, const long long *off, int *align, int *dist)
+// strand == nullptr: pia_align, every read as it stands.  Otherwise pass 1 runs job 2j + s = read j on strand s, and the reads
+// of pass 2 carry the strand that won.
+static int align_reads(pia_ctx *c, int nreads, const char *bases, const long long *off, int *align, int *dist, int *dist_other,
+                       unsigned char *strand)
 {
     if (!c || nreads < 0 || !off || (nreads && (!bases || !align || !dist))) return PWR_ERR_ARG;
+    const int ns = strand ? 2 : 1;                                                    // jobs of pass 1 per read
     if (nreads == 0) return PWR_OK;
     if (hipSetDevice(c->device) != hipSuccess) return PWR_ERR_DEVICE;
     for (int j = 0; j < nreads; ++j) {
@@ -324,38 +347,59 @@ static int align_reads(pia_ctx *c, int nreads, const char *bases, const long lon
     for (double &t : c->t_ms) t = 0;
     const long long b0 = off[0], nb = off[nreads] - off[0];
     for (long long i = 0; i < nb; ++i) if (!ia_is_base(bases[b0 + i])) return PWR_ERR_INPUT;
-    std::vector<IaRead> hr(nreads);
-    std::vector<int> order(nreads);
-    for (int j = 0; j < nreads; ++j) {
-        hr[j].boff = off[j] - b0; hr[j].coff = 0; hr[j].L1 = (int)(off[j + 1] - off[j]); hr[j].dist = 0; hr[j].entry = c->L2 - 1; hr[j].nl = 0;
-        c->cells += (unsigned long long)hr[j].L1 * (unsigned long long)c->L2;
+    if ((long long)nreads * ns > 0x7fffffff) return PWR_ERR_RANGE;
+    const int njobs = nreads * ns;
+    std::vector<IaRead> hr(njobs);
+    std::vector<int> order(njobs);
+    for (int k = 0; k < njobs; ++k) {
+        const int j = k / ns;
+        hr[k].boff = off[j] - b0; hr[k].coff = 0; hr[k].L1 = (int)(off[j + 1] - off[j]); hr[k].dist = 0; hr[k].entry = c->L2 - 1;
+        hr[k].nl = (k % ns) ? IA_REVERSE : 0;
+        c->cells += (unsigned long long)hr[k].L1 * (unsigned long long)c->L2;
     }
     // the longest reads first: the waves that run longest start first
     std::iota(order.begin(), order.end(), 0);
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return hr[a].L1 > hr[b].L1; });
     if (c->L2 == 0) {                                                                 // nothing to align to: every base unaligned
         for (long long i = 0; i < nb; ++i) align[b0 + i] = -1;
-        for (int j = 0; j < nreads; ++j) dist[j] = hr[j].L1;                          // Row[-1 + 0] is never read by the reference; E(x,-1) = x + 1
+        for (int j = 0; j < nreads; ++j) dist[j] = hr[j * ns].L1;                     // Row[-1 + 0] is never read by the reference; E(x,-1) = x + 1
+        if (strand) for (int j = 0; j < nreads; ++j) { strand[j] = 0; if (dist_other) dist_other[j] = dist[j]; }
         return PWR_OK;
     }
     DevBufs d;
     HIPC(hipEventCreate(&d.e0)); HIPC(hipEventCreate(&d.e1));
-    d.bases = d.mem.get<char>(nb); d.reads = d.mem.get<IaRead>(nreads); d.order = d.mem.get<int>(nreads); d.align = d.mem.get<int>(nb);
+    d.bases = d.mem.get<char>(nb); d.reads = d.mem.get<IaRead>(njobs); d.order = d.mem.get<int>(njobs); d.align = d.mem.get<int>(nb);
     if (!d.bases || !d.reads || !d.order || !d.align) return PWR_ERR_NOMEM;
     if (nb) HIPC(hipMemcpyAsync(d.bases, bases + b0, nb, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipMemcpyAsync(d.reads, hr.data(), sizeof(IaRead) * nreads, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipMemcpyAsync(d.order, order.data(), sizeof(int) * nreads, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(d.reads, hr.data(), sizeof(IaRead) * njobs, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(d.order, order.data(), sizeof(int) * njobs, hipMemcpyHostToDevice, c->stream));
     float ms = 0;
     HIPC(hipStreamSynchronize(c->stream));
     c->t_ms[1] = now_ms() - t_start;
-    // pass 1: distance and entry column of every read
+    // pass 1: distance and entry column of every job
     HIPC(hipEventRecord(d.e0, c->stream));
-    launch_bits<1>(c, false, nreads, d.bases, d.reads, d.order, nullptr, nullptr, c->stream);
+    launch_bits<1>(c, false, strand != nullptr, njobs, d.bases, d.reads, d.order, nullptr, nullptr, c->stream);
     HIPC(hipGetLastError());
     HIPC(hipEventRecord(d.e1, c->stream));
-    HIPC(hipMemcpyAsync(hr.data(), d.reads, sizeof(IaRead) * nreads, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipMemcpyAsync(hr.data(), d.reads, sizeof(IaRead) * njobs, hipMemcpyDeviceToHost, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
     if (hipEventElapsedTime(&ms, d.e0, d.e1) == hipSuccess) { c->fill_ms += ms; c->t_ms[2] = ms; }
+    if (strand) {
+        // the choice: the reverse strand only where it is strictly nearer.  From here on hr[j] is read j in the orientation
+        // taken, and pass 2 is what it is for pia_align on the turned reads.
+        for (int j = 0; j < nreads; ++j) {
+            const IaRead &f = hr[2 * j], &r = hr[2 * j + 1];
+            strand[j] = r.dist < f.dist;
+            if (dist_other) dist_other[j] = strand[j] ? f.dist : r.dist;
+            const IaRead taken = strand[j] ? r : f;
+            hr[j] = taken;
+        }
+        hr.resize(nreads);
+        order.resize(nreads);
+        std::iota(order.begin(), order.end(), 0);
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return hr[a].L1 > hr[b].L1; });
+        HIPC(hipMemcpyAsync(d.order, order.data(), sizeof(int) * nreads, hipMemcpyHostToDevice, c->stream));
+    }
     // pass 2 in batches whose bands fit the budget, IA_NBUF of them in flight, each with its buffer and stream: the tail of
     // one batch (its longest reads) runs beside the bulk of the next ones
     // The budget per buffer: 22 GB by default, but never more than the card has to spare right now (other contexts or ranks
@@ -375,8 +419,9 @@ static int align_reads(pia_ctx *c, int nreads, const char *bases, const long lon
         size_t words = 0;
         for (int k = 0; k < nreads; ++k) {
             IaRead &r = hr[order[k]];
-            r.nl = (2 * r.dist) / (32 * c->WPL) + 2;
-            const size_t w = (size_t)r.L1 * (size_t)r.nl * WPS;
+            const int nl = (2 * r.dist) / (32 * c->WPL) + 2;
+            r.nl = nl | (r.nl & IA_REVERSE);
+            const size_t w = (size_t)r.L1 * (size_t)nl * WPS;
             if (words && (words + w) * sizeof(uint2) > budget) { bend.push_back(k); maxwords = std::max(maxwords, words); words = 0; }
             r.coff = (long long)words;
             words += (w + 15) & ~(size_t)15;                                          // every read's band starts on its own 128-byte line
@@ -404,7 +449,7 @@ static int align_reads(pia_ctx *c, int nreads, const char *bases, const long lon
         const int k1 = bend[bi], n = k1 - k0;
         hipStream_t st = c->streams[bi % IA_NBUF];
         HIPC(hipEventRecord(d.ev[2 * bi], st));
-        launch_bits<1>(c, true, n, d.bases, d.reads, d.order + k0, c->codes[bi % IA_NBUF], d.align, st);
+        launch_bits<1>(c, true, strand != nullptr, n, d.bases, d.reads, d.order + k0, c->codes[bi % IA_NBUF], d.align, st);
         HIPC(hipGetLastError());
         HIPC(hipEventRecord(d.ev[2 * bi + 1], st));
         k0 = k1;
@@ -430,5 +475,15 @@ static int align_reads(pia_ctx *c, int nreads, const char *bases, const long lon
 
 extern "C" int pia_align(pia_ctx *c, int nreads, const char *bases, const long long *off, int *align, int *dist)
 {
-    return abi_guard([&] { return align_reads(c, nreads, bases, off, align, dist); });
+    return abi_guard([&] { return align_reads(c, nreads, bases, off, align, dist, nullptr, nullptr); });
+}
+
+extern "C" int pia_align_strands(pia_ctx *c, int nreads, const char *bases, const long long *off, int *align, int *dist,
+                                 int *dist_other, unsigned char *strand)
+{
+    return abi_guard([&] {
+        if (nreads > 0 && (!dist_other || !strand)) return (int)PWR_ERR_ARG;
+        unsigned char none = 0;                                                       // (nreads == 0: nothing is written)
+        return align_reads(c, nreads, bases, off, align, dist, dist_other, strand ? strand : &none);
+    });
 }

@@ -76,6 +76,22 @@ int pia_read_fasta(const char *path, int *nreads, char **bases, long long **off)
     return PWR_OK;
 }
 
+int pia_turn(int nreads, const char *bases, const long long *off, const unsigned char *strand, char *out)
+{
+    if (nreads < 0 || !off || (nreads && (!bases || !strand || !out))) return PWR_ERR_ARG;
+    for (int j = 0; j < nreads; j++) {
+        const long long a = off[j], L = off[j + 1] - off[j];
+        if (L < 0) return PWR_ERR_ARG;
+        for (long long x = 0; x < L; x++) {
+            const char ch = strand[j] ? bases[a + L - 1 - x] : bases[a + x];
+            if (!base_of(ch)) return PWR_ERR_INPUT;
+            /* (ch >> 1) & 3: a c t g -> 0 1 2 3, as in the kernels; the complement keeps bit 5, the letter's case */
+            out[a + x] = strand[j] ? (char)("tgac"[(ch >> 1) & 3] ^ (~ch & 0x20)) : ch;
+        }
+    }
+    return PWR_OK;
+}
+
 int pia_build_msa(const char *msa_path, const char *class_path, int nreads, const char *bases, const long long *off,
                   const int *align, const int *dist, double cutoff, int templ_len)
 {
@@ -130,9 +146,25 @@ int pia_build_msa(const char *msa_path, const char *class_path, int nreads, cons
 int pia_run_files(const char *templ_path, const char *reads_path, const char *msa_path, const char *class_path,
                   double cutoff, int cutoff_given, int device, FILE *log)
 {
-    char *templ = NULL, *bases = NULL;
+    return pia_run_files_strands(templ_path, reads_path, msa_path, class_path, NULL, cutoff, cutoff_given, device, log);
+}
+
+static int write_strands(const char *path, int n, const unsigned char *strand)
+{
+    FILE *f = fopen(path, "w");
+    if (!f) return PWR_ERR_IO;
+    for (int j = 0; j < n; j++) fputs(strand[j] ? "-\n" : "+\n", f);
+    const int bad = ferror(f);
+    return (fclose(f) != 0 || bad) ? PWR_ERR_IO : PWR_OK;
+}
+
+int pia_run_files_strands(const char *templ_path, const char *reads_path, const char *msa_path, const char *class_path,
+                          const char *strand_path, double cutoff, int cutoff_given, int device, FILE *log)
+{
+    char *templ = NULL, *bases = NULL, *turned = NULL;
     long long *off = NULL;
-    int *align = NULL, *dist = NULL;
+    int *align = NULL, *dist = NULL, *other = NULL;
+    unsigned char *strand = NULL;
     int L2 = 0, n = 0, rc;
     pia_ctx *ctx = NULL;
     if (cutoff_given) fprintf(log, "errorcutoff %f.\n", cutoff);                   /* IA:722 */
@@ -144,15 +176,25 @@ int pia_run_files(const char *templ_path, const char *reads_path, const char *ms
     fprintf(log, "read count %d\n", n);                                            /* IA:750 */
     align = malloc(sizeof(int) * (size_t)(off[n] > 0 ? off[n] : 1));
     dist = malloc(sizeof(int) * (size_t)(n > 0 ? n : 1));
-    rc = (align && dist) ? pia_create(&ctx, templ, L2, device) : PWR_ERR_NOMEM;
-    if (rc == PWR_OK) rc = pia_align(ctx, n, bases, off, align, dist);             /* IA:754 Parallel_Aligning */
+    if (strand_path) {
+        turned = malloc((size_t)(off[n] > 0 ? off[n] : 1));
+        other = malloc(sizeof(int) * (size_t)(n > 0 ? n : 1));
+        strand = malloc((size_t)(n > 0 ? n : 1));
+    }
+    rc = (align && dist && (!strand_path || (turned && other && strand))) ? pia_create(&ctx, templ, L2, device) : PWR_ERR_NOMEM;
+    if (rc == PWR_OK && !strand_path) rc = pia_align(ctx, n, bases, off, align, dist);   /* IA:754 Parallel_Aligning */
+    if (rc == PWR_OK && strand_path) {
+        rc = pia_align_strands(ctx, n, bases, off, align, dist, other, strand);
+        if (rc == PWR_OK) rc = pia_turn(n, bases, off, strand, turned);
+        if (rc == PWR_OK) rc = write_strands(strand_path, n, strand);
+    }
     if (rc == PWR_OK) {
         fprintf(log, "Writing the msa.\n");                                        /* IA:756 */
-        rc = pia_build_msa(msa_path, class_path, n, bases, off, align, dist, cutoff, L2);
+        rc = pia_build_msa(msa_path, class_path, n, strand_path ? turned : bases, off, align, dist, cutoff, L2);
         if (rc == PWR_OK) fprintf(log, "\nFiles written.\n");                      /* IA:658 */
     }
     if (rc != PWR_OK) fprintf(log, "InitialAligner: %s\n", pwr_strerror(rc));
     pia_destroy(ctx);
-    free(templ); free(bases); free(off); free(align); free(dist);
+    free(templ); free(bases); free(off); free(align); free(dist); free(turned); free(other); free(strand);
     return rc == PWR_OK ? 0 : 1;
 }

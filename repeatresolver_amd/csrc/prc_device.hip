@@ -19,6 +19,12 @@
 // {first column, last column, minimum, largest column holding the minimum}: all that the scan needs (prc_scan_runs).  A job
 // has room for `cap` runs; it always counts all of them, and the host re-runs every job whose count exceeds its room with
 // exactly that much room, so nothing is dropped.
+//
+// Both strands (prc_occurrences_strands, prc_cut_strands): a job carries its strand.  Base y of rc(read) is the complement of
+// read[L-1-y], and with the codes a c g t -> 0 1 3 2 the complement flips bit 1 of the code, bit 2 of the character.  A reverse
+// job therefore differs from a forward one only where the kernel loads a base: it walks the read from its far end and flips
+// that bit.  Its columns y, and so its runs and positions, are in the coordinates of rc(read).  The kernels that look at a
+// job's strand are instances of their own (BOTH): prc_occurrences and prc_cut run the ones that do not, the code they always ran.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -43,11 +49,11 @@ struct RcJob {
     int L;                          // read length
     int pat;                        // piece: 0 = piece 0, 1 = piece parts-1
     int cap;                        // runs it has room for
-    int pad;
+    int strand;                     // 1: the job maps the piece into rc(read), read from the same bases backwards
 };
 
 // one group of G lanes per job; 64 / G groups per wave (one wave per block)
-template <int WPL>
+template <int WPL, bool BOTH>
 __global__ __launch_bounds__(64) void k_rc_rows(const uint32_t *__restrict__ planes, int nwords, int len, int cutoff,
                                                 const char *__restrict__ bases, const RcJob *__restrict__ jobs,
                                                 const int *__restrict__ order, int njobs, int G, int4 *__restrict__ runs,
@@ -73,20 +79,23 @@ __global__ __launch_bounds__(64) void k_rc_rows(const uint32_t *__restrict__ pla
         P0[w] = in ? pl[g] : 0u; P1[w] = in ? pl[nwords + g] : 0u; V[w] = in ? pl[2 * nwords + g] : 0u;
         Pv[w] = ~0u; Mv[w] = 0u;                            // column -1: M(x,-1) - M(x-1,-1) = +1
     }
-    const char *read = bases + jb.boff;
+    // a reverse job walks the read from its far end, base y at read[-y], with the complement's bit flipped
+    const int strand = BOTH ? jb.strand : 0;
+    const char *read = bases + jb.boff + (strand ? L - 1 : 0);
+    const int dir = strand ? -1 : 1, flip = strand << 2;
     // every group runs L + toplane steps; the wave runs its longest group's
     int steps = L > 0 ? L + toplane : 0;
     for (int o = 32; o > 0; o >>= 1) steps = max(steps, __shfl_xor(steps, o));
     const bool active = lg <= toplane;
     int score = len, nrun = 0, inrun = 0, lo = 0, mn = 0, ey = 0;
     int msg = 0;                                            // horizontal delta leaving the lane's last word: +1 (bit 0), -1 (bit 1)
-    int ch = (active && L > 0 && lg == 0) ? read[0] : 0;   // base of the next step, loaded one step ahead
+    int ch = (active && L > 0 && lg == 0) ? read[0] ^ flip : 0;   // base of the next step, loaded one step ahead
     for (int tau = 0; tau < steps; ++tau) {
         int m = __shfl_up(msg, 1);
         if (lg == 0) m = 0;                                 // M(-1,y) - M(-1,y-1) = 0: a free start anywhere in the read
         const int y = tau - lg;
         const int c = ch;
-        if (active && y + 1 >= 0 && y + 1 < L) ch = read[y + 1];
+        if (active && y + 1 >= 0 && y + 1 < L) ch = read[dir * (y + 1)] ^ flip;
         if (active && y >= 0 && y < L) {
             const uint32_t r0 = (c >> 1) & 1 ? ~0u : 0u, r1 = (c >> 2) & 1 ? ~0u : 0u;   // a c g t -> 0 1 3 2
             uint32_t hp = m & 1, hn = (m >> 1) & 1, tp = 0, tn = 0;
@@ -176,14 +185,15 @@ extern "C" int prc_get_stats(prc_ctx *c, unsigned long long *cells, double *kern
 }
 
 template <int WPL>
-static void launch_rows(int wpl, dim3 grid, hipStream_t st, const uint32_t *planes, int nwords, int len, int cutoff, const char *bases,
+static void launch_rows(int wpl, bool both, dim3 grid, hipStream_t st, const uint32_t *planes, int nwords, int len, int cutoff, const char *bases,
                         const RcJob *jobs, const int *order, int njobs, int G, int4 *runs, int *counts)
 {
     if (wpl == WPL) {
-        hipLaunchKernelGGL((k_rc_rows<WPL>), grid, dim3(64), 0, st, planes, nwords, len, cutoff, bases, jobs, order, njobs, G, runs, counts);
+        if (both) hipLaunchKernelGGL((k_rc_rows<WPL, true>), grid, dim3(64), 0, st, planes, nwords, len, cutoff, bases, jobs, order, njobs, G, runs, counts);
+        else hipLaunchKernelGGL((k_rc_rows<WPL, false>), grid, dim3(64), 0, st, planes, nwords, len, cutoff, bases, jobs, order, njobs, G, runs, counts);
         return;
     }
-    if constexpr (WPL < RC_MAXWPL) launch_rows<WPL + 1>(wpl, grid, st, planes, nwords, len, cutoff, bases, jobs, order, njobs, G, runs, counts);
+    if constexpr (WPL < RC_MAXWPL) launch_rows<WPL + 1>(wpl, both, grid, st, planes, nwords, len, cutoff, bases, jobs, order, njobs, G, runs, counts);
 }
 
 struct RcBufs {                     // freed on every way out
@@ -197,9 +207,10 @@ struct RcBufs {                     // freed on every way out
     }
 };
 
-// The rows of every (read, queried piece) job; on return run_off[k .. k+1) delimits job k's runs in `runs` (ascending columns).
+// The rows of every (read, strand, queried piece) job, k = (j * ns + s) * nq + q with ns strands per read (1: forward only);
+// on return run_off[k .. k+1) delimits job k's runs in `runs` (ascending columns of that orientation).
 static int rc_rows(prc_ctx *c, int nreads, const char *bases, const long long *off, int parts, int overlap, double error_cutoff,
-                   int *nq_out, int *len_out, std::vector<long long> &run_off, std::vector<int> &runs)
+                   int ns, int *nq_out, int *len_out, std::vector<long long> &run_off, std::vector<int> &runs)
 {
     if (!c || nreads < 0 || !off || (nreads && !bases)) return PWR_ERR_ARG;
     if (parts < 1) return PWR_ERR_ARG;                                             // RC:583 divides by it
@@ -214,10 +225,10 @@ static int rc_rows(prc_ctx *c, int nreads, const char *bases, const long long *o
     }
     const long long b0 = nreads ? off[0] : 0, nb = nreads ? off[nreads] - off[0] : 0;
     for (long long i = 0; i < nb; ++i) if (!rc_is_base(bases[b0 + i])) return PWR_ERR_INPUT;
-    const long long njobs = (long long)nreads * nq;
+    const long long njobs = (long long)nreads * ns * nq;
     run_off.assign((size_t)njobs + 1, 0);
     runs.clear();
-    for (int j = 0; j < nreads; ++j) c->cells += (unsigned long long)(off[j + 1] - off[j]) * (unsigned long long)len * nq;
+    for (int j = 0; j < nreads; ++j) c->cells += (unsigned long long)(off[j + 1] - off[j]) * (unsigned long long)len * nq * ns;
     // len = 0: the last row is row -1, all 0, never below a cutoff of 0 (RC:534); a cutoff <= 0 is never undercut either
     if (len == 0 || cutoff <= 0 || njobs == 0) return PWR_OK;
     if (len > PRC_MAX_PART) return PWR_ERR_RANGE;
@@ -244,11 +255,12 @@ static int rc_rows(prc_ctx *c, int nreads, const char *bases, const long long *o
     order.reserve((size_t)njobs);
     long long roff = 0;
     for (int j = 0; j < nreads; ++j)
-        for (int q = 0; q < nq; ++q) {
-            RcJob &jb = hj[(size_t)j * nq + q];
-            jb.boff = off[j] - b0; jb.L = (int)(off[j + 1] - off[j]); jb.pat = q; jb.cap = PRC_RUN_CAP; jb.pad = 0;
+        for (int sq = 0; sq < ns * nq; ++sq) {
+            const int k = j * ns * nq + sq;
+            RcJob &jb = hj[(size_t)k];
+            jb.boff = off[j] - b0; jb.L = (int)(off[j + 1] - off[j]); jb.pat = sq % nq; jb.cap = PRC_RUN_CAP; jb.strand = sq / nq;
             jb.roff = roff; roff += jb.cap;
-            if (jb.L > 0) order.push_back(j * nq + q);
+            if (jb.L > 0) order.push_back(k);
         }
     // the longest reads first: neighbours in a wave run about as long, and the waves that run longest start first
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return hj[a].L > hj[b].L; });
@@ -268,7 +280,7 @@ static int rc_rows(prc_ctx *c, int nreads, const char *bases, const long long *o
     const int per = 64 / G;
     float ms = 0;
     HIPC(hipEventRecord(d.e0, c->stream));
-    launch_rows<1>(wpl, dim3((unsigned)((order.size() + per - 1) / per)), c->stream, d.planes, nwords, len, cutoff, d.bases, d.jobs,
+    launch_rows<1>(wpl, ns == 2, dim3((unsigned)((order.size() + per - 1) / per)), c->stream, d.planes, nwords, len, cutoff, d.bases, d.jobs,
                    d.order, (int)order.size(), G, d.runs, d.counts);
     HIPC(hipGetLastError());
     HIPC(hipEventRecord(d.e1, c->stream));
@@ -292,7 +304,7 @@ static int rc_rows(prc_ctx *c, int nreads, const char *bases, const long long *o
             hipMemcpyAsync(d.order, again.data(), sizeof(int) * again.size(), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
             hipEventRecord(d.e0, c->stream) != hipSuccess) rc = PWR_ERR_DEVICE;
         if (rc == PWR_OK) {
-            launch_rows<1>(wpl, dim3((unsigned)((again.size() + per - 1) / per)), c->stream, d.planes, nwords, len, cutoff, d.bases,
+            launch_rows<1>(wpl, ns == 2, dim3((unsigned)((again.size() + per - 1) / per)), c->stream, d.planes, nwords, len, cutoff, d.bases,
                            d.jobs, d.order, (int)again.size(), G, runs2, d.counts);
             if (hipGetLastError() != hipSuccess || hipEventRecord(d.e1, c->stream) != hipSuccess ||
                 hipMemcpyAsync(counts2.data(), d.counts, sizeof(int) * hj.size(), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
@@ -319,15 +331,15 @@ static int rc_rows(prc_ctx *c, int nreads, const char *bases, const long long *o
 }
 
 static int occurrences(prc_ctx *c, int nreads, const char *bases, const long long *off, int parts, int overlap, double error_cutoff,
-                       long long *pos_off, int **pos)
+                       int ns, long long *pos_off, int **pos)
 {
     if (!pos_off || !pos) return PWR_ERR_ARG;
     int nq = 0, len = 0;
     std::vector<long long> run_off;
     std::vector<int> runs;
-    const int rc = rc_rows(c, nreads, bases, off, parts, overlap, error_cutoff, &nq, &len, run_off, runs);
+    const int rc = rc_rows(c, nreads, bases, off, parts, overlap, error_cutoff, ns, &nq, &len, run_off, runs);
     if (rc != PWR_OK) return rc;
-    const long long njobs = (long long)nreads * nq;
+    const long long njobs = (long long)nreads * ns * nq;
     int *p = (int *)malloc(sizeof(int) * (size_t)std::max<long long>(run_off[njobs], 1));
     if (!p) return PWR_ERR_NOMEM;
     pos_off[0] = 0;
@@ -342,37 +354,62 @@ static int occurrences(prc_ctx *c, int nreads, const char *bases, const long lon
 extern "C" int prc_occurrences(prc_ctx *c, int nreads, const char *bases, const long long *off, int parts, int overlap,
                                double error_cutoff, long long *pos_off, int **pos)
 {
-    return abi_guard([&] { return occurrences(c, nreads, bases, off, parts, overlap, error_cutoff, pos_off, pos); });
+    return abi_guard([&] { return occurrences(c, nreads, bases, off, parts, overlap, error_cutoff, 1, pos_off, pos); });
 }
 
+extern "C" int prc_occurrences_strands(prc_ctx *c, int nreads, const char *bases, const long long *off, int parts, int overlap,
+                                       double error_cutoff, long long *pos_off, int **pos)
+{
+    return abi_guard([&] { return occurrences(c, nreads, bases, off, parts, overlap, error_cutoff, 2, pos_off, pos); });
+}
+
+// nfwd == nullptr: prc_cut.  Otherwise FullAnalysis once per orientation, the two lists merged into the read's coordinates.
 static int cut(prc_ctx *c, int nreads, const char *bases, const long long *off, int parts, int overlap, double error_cutoff, int *ncut,
-               int **cuts)
+               int **cuts, int *nfwd, int *nrev)
 {
     if (!ncut || !cuts) return PWR_ERR_ARG;
+    const int ns = nfwd ? 2 : 1;
     int nq = 0, len = 0;
     std::vector<long long> run_off;
     std::vector<int> runs;
-    const int rc = rc_rows(c, nreads, bases, off, parts, overlap, error_cutoff, &nq, &len, run_off, runs);
+    const int rc = rc_rows(c, nreads, bases, off, parts, overlap, error_cutoff, ns, &nq, &len, run_off, runs);
     if (rc != PWR_OK) return rc;
-    const long long njobs = (long long)nreads * nq;
-    // positions <= runs per job; cut points <= 3 * n0 + 2 * nL + 1 per read
+    const long long njobs = (long long)nreads * ns * nq;
+    // positions <= runs per job; cut points <= 3 * n0 + 2 * nL + 1 per read and orientation
     std::vector<int> pos((size_t)std::max<long long>(run_off[njobs], 1));
     std::vector<long long> cut_off((size_t)nreads + 1, 0);
-    for (int j = 0; j < nreads; ++j) cut_off[j + 1] = cut_off[j] + 3 * (run_off[(size_t)(j + 1) * nq] - run_off[(size_t)j * nq]) + 1;
+    long long widest = 1;
+    for (int j = 0; j < nreads; ++j) {
+        const long long room = 3 * (run_off[(size_t)(j + 1) * ns * nq] - run_off[(size_t)j * ns * nq]) + ns;
+        cut_off[j + 1] = cut_off[j] + room;
+        widest = std::max(widest, room);
+    }
+    std::vector<int> both((size_t)(ns == 2 ? 2 * widest : 0));                          // one read's two lists before the merge
     int *out = (int *)malloc(sizeof(int) * (size_t)std::max<long long>(cut_off[nreads], 1));
     if (!out) return PWR_ERR_NOMEM;
     long long w = 0;
     for (int j = 0; j < nreads; ++j) {
-        const long long k0 = (long long)j * nq;
-        int *p0 = pos.data() + run_off[k0];
-        const int n0 = prc_scan_runs(runs.data() + run_off[k0] * 4, (int)(run_off[k0 + 1] - run_off[k0]), len, p0);
-        int *pL = p0, nL = n0;
-        if (nq == 2) {
-            pL = pos.data() + run_off[k0 + 1];
-            nL = prc_scan_runs(runs.data() + run_off[k0 + 1] * 4, (int)(run_off[k0 + 2] - run_off[k0 + 1]), len, pL);
+        const int readlen = (int)(off[j + 1] - off[j]);
+        int n_of[2] = {0, 0};
+        for (int s = 0; s < ns; ++s) {
+            const long long k0 = ((long long)j * ns + s) * nq;
+            int *p0 = pos.data() + run_off[k0];
+            const int n0 = prc_scan_runs(runs.data() + run_off[k0] * 4, (int)(run_off[k0 + 1] - run_off[k0]), len, p0);
+            int *pL = p0, nL = n0;
+            if (nq == 2) {
+                pL = pos.data() + run_off[k0 + 1];
+                nL = prc_scan_runs(runs.data() + run_off[k0 + 1] * 4, (int)(run_off[k0 + 2] - run_off[k0 + 1]), len, pL);
+            }
+            int *dst = ns == 2 ? both.data() + (size_t)s * widest : out + w;
+            n_of[s] = prc_select_cuts(parts, len, c->T, readlen, p0, n0, pL, nL, dst);
+            if (n_of[s] < 0) { free(out); return n_of[s]; }
         }
-        const int n = prc_select_cuts(parts, len, c->T, (int)(off[j + 1] - off[j]), p0, n0, pL, nL, out + w);
-        if (n < 0) { free(out); return n; }
+        int n = n_of[0];
+        if (ns == 2) {
+            n = prc_merge_cuts(readlen, n_of[0], both.data(), n_of[1], both.data() + widest, out + w);
+            if (n < 0) { free(out); return n; }
+            nfwd[j] = n_of[0]; nrev[j] = n_of[1];
+        }
         ncut[j] = n;
         w += n;
     }
@@ -383,5 +420,14 @@ static int cut(prc_ctx *c, int nreads, const char *bases, const long long *off, 
 extern "C" int prc_cut(prc_ctx *c, int nreads, const char *bases, const long long *off, int parts, int overlap, double error_cutoff,
                        int *ncut, int **cuts)
 {
-    return abi_guard([&] { return cut(c, nreads, bases, off, parts, overlap, error_cutoff, ncut, cuts); });
+    return abi_guard([&] { return cut(c, nreads, bases, off, parts, overlap, error_cutoff, ncut, cuts, nullptr, nullptr); });
+}
+
+extern "C" int prc_cut_strands(prc_ctx *c, int nreads, const char *bases, const long long *off, int parts, int overlap,
+                               double error_cutoff, int *ncut, int **cuts, int *nfwd, int *nrev)
+{
+    return abi_guard([&] {
+        if (!nfwd || !nrev) return (int)PWR_ERR_ARG;
+        return cut(c, nreads, bases, off, parts, overlap, error_cutoff, ncut, cuts, nfwd, nrev);
+    });
 }

@@ -198,6 +198,20 @@ int prc_select_cuts(int parts, int len, int templ_len, int readlen, const int *p
     return nc;
 }
 
+/* A cut of rc(read) at c is a cut of read at readlen - c */
+int prc_merge_cuts(int readlen, int nf, const int *fwd, int nr, const int *rev, int *out)
+{
+    if (nf < 0 || nr < 0 || (nf && !fwd) || (nr && !rev) || ((nf || nr) && !out)) return PWR_ERR_ARG;
+    int n = 0;
+    for (int i = 0; i < nf; i++) out[n++] = fwd[i];
+    for (int i = 0; i < nr; i++) out[n++] = readlen - rev[i];
+    qsort(out, (size_t)n, sizeof(int), cmp_int);
+    int m = 0;
+    for (int i = 0; i < n; i++)
+        if (m == 0 || out[i] != out[m - 1]) out[m++] = out[i];
+    return m;
+}
+
 void prc_free(void *p)
 {
     free(p);
@@ -251,10 +265,16 @@ int prc_write_info(const char *path, int nrec, const int *ncut)
 int prc_run_files(const char *templ_path, const char *reads_path, const char *seq_path, const char *info_path, int parts,
                   int overlap, double error_cutoff, int wiggleroom, int device, FILE *log)
 {
+    return prc_run_files_strands(templ_path, reads_path, seq_path, info_path, parts, overlap, error_cutoff, wiggleroom, 0, device, log);
+}
+
+int prc_run_files_strands(const char *templ_path, const char *reads_path, const char *seq_path, const char *info_path, int parts,
+                          int overlap, double error_cutoff, int wiggleroom, int both_strands, int device, FILE *log)
+{
     fprintf(log, "parts %d, overlap %d, wiggleroom %d, error_cutoff %f\n", parts, overlap, wiggleroom, error_cutoff);   /* RC:1034 */
     char *bases = NULL, *last = NULL, *templ = NULL, *out = NULL;
     long long *off = NULL, *ooff = NULL;
-    int *ncut = NULL, *cuts = NULL, *nseq = NULL, *ninfo = NULL, *scuts = NULL;
+    int *ncut = NULL, *cuts = NULL, *nseq = NULL, *ninfo = NULL, *scuts = NULL, *nside = NULL;
     int n = 0, P = 0, T = 0, rc = PWR_OK, ret = 1;
     prc_ctx *ctx = NULL;
     if (prc_read_fasta(reads_path, &n, &bases, &off, &last, &P)) { fprintf(log, "No Reads.\n"); fflush(log); return 1; }   /* RC:865 */
@@ -281,8 +301,11 @@ int prc_run_files(const char *templ_path, const char *reads_path, const char *se
     if (n >= 2) {
         /* FullAnalysis of every record as written (record n-2's own analysis is overwritten by the last one's, RC:659) */
         ncut = malloc(sizeof(int) * (size_t)nout);
-        rc = ncut ? prc_create(&ctx, templ, T, device) : PWR_ERR_NOMEM;
-        if (rc == PWR_OK) rc = prc_cut(ctx, nout, out, ooff, parts, overlap, error_cutoff, ncut, &cuts);
+        if (both_strands) nside = malloc(sizeof(int) * 2 * (size_t)nout);
+        rc = (ncut && (!both_strands || nside)) ? prc_create(&ctx, templ, T, device) : PWR_ERR_NOMEM;
+        if (rc == PWR_OK && !both_strands) rc = prc_cut(ctx, nout, out, ooff, parts, overlap, error_cutoff, ncut, &cuts);
+        if (rc == PWR_OK && both_strands)
+            rc = prc_cut_strands(ctx, nout, out, ooff, parts, overlap, error_cutoff, ncut, &cuts, nside, nside + nout);
         if (rc != PWR_OK) goto fail;
         for (int i = 0; i < nout; i++) {
             const int c = i < n - 2 ? ncut[i] : ncut[n - 1];
@@ -314,7 +337,7 @@ fail:
 done:
     prc_destroy(ctx);
     free(bases); free(off); free(last); free(templ); free(out); free(ooff);
-    free(ncut); prc_free(cuts); free(nseq); free(ninfo); free(scuts);
+    free(ncut); prc_free(cuts); free(nseq); free(ninfo); free(scuts); free(nside);
     fflush(log);
     return ret;
 }

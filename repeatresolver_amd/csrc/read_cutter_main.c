@@ -1,5 +1,6 @@
 /* Drop-in for the reference's `ReadCutter` (ReadCutter.c main(), RC:939-1112): same argv, same files, same stdout including the
- * progress lines; the edit-distance rows run on the GPU behind include/prc.h.  Extra flag: -g <device>. */
+ * progress lines; the edit-distance rows run on the GPU behind include/prc.h.  Extra flags: -g <device>, -b 1: reads may lie
+ * on either strand (prc_cut_strands); without it nothing changes. */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -14,6 +15,7 @@ static void help(void)
     printf("-e <0.30>  is the mapping error cutoff being used to detect occurences of parts in reads\n");
     printf("-w <150>   restricts how far apart and close together mappings can be.\n");
     printf("-l <0>     is used to create parts which overlap by l bases.\n");
+    printf("-b <0>     1: reads may lie on either strand; the parts are also mapped into each read's reverse complement.\n");
     exit(0);
 }
 
@@ -32,7 +34,7 @@ int main(int argc, char **argv)
     printf("outputfile: %s\n", out_seq);
     printf("readseqfile: %s\n", out_info);
     const char *seq = out_seq, *info = out_info;
-    int parts = 60, overlap = 0, wiggleroom = 150, device = 0;
+    int parts = 60, overlap = 0, wiggleroom = 150, device = 0, both_strands = 0;
     double error_cutoff = 0.30;
     for (int i = 1; i < argc; i++) {                                                                                   /* RC:991-1030 */
         if (argv[i][0] != '-') continue;
@@ -44,10 +46,12 @@ int main(int argc, char **argv)
         if (argv[i][1] == 'w' && has) wiggleroom = atoi(argv[i + 1]);
         if (argv[i][1] == 'e' && has) error_cutoff = atof(argv[i + 1]);
         if (argv[i][1] == 'g' && has) device = atoi(argv[i + 1]);
+        if (argv[i][1] == 'b' && has) both_strands = atoi(argv[i + 1]) != 0;
         if (argv[i][1] == 'h') help();
     }
     fflush(stdout);
-    const int rc = prc_run_files(templ_path, reads_path, seq, info, parts, overlap, error_cutoff, wiggleroom, device, stdout);
+    const int rc = prc_run_files_strands(templ_path, reads_path, seq, info, parts, overlap, error_cutoff, wiggleroom, both_strands,
+                                         device, stdout);
     free(out_seq); free(out_info);
     return rc;
 }

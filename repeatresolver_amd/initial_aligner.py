@@ -61,6 +61,45 @@ class InitialAligner:
             raise PwrError(rc, self._lib.pwr_strerror(rc).decode())
         return [align[off[j]:off[j + 1]].copy() for j in range(n)], dist[:n].copy()
 
+    def align_strands(self, reads):
+        """align for reads that may lie on either strand (pia_align_strands): every read is aligned as it stands and as its
+        reverse complement, and the nearer orientation is kept, the forward one on a tie.  Returns (placements, distances,
+        strands, other_distances): strands[j] = 1 where the reverse complement was taken, placements[j][x] = template position
+        of base x of the *turned* read (see turned), distances[j] the smaller distance, other_distances[j] the one of the
+        orientation not taken."""
+        reads = [_clean(r) for r in reads]
+        n = len(reads)
+        off = np.zeros(n + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(r) for r in reads])
+        align = np.empty(max(int(off[-1]), 1), dtype=np.int32)
+        dist = np.empty(max(n, 1), dtype=np.int32)
+        other = np.empty(max(n, 1), dtype=np.int32)
+        strand = np.zeros(max(n, 1), dtype=np.uint8)
+        pi = ctypes.POINTER(ctypes.c_int)
+        rc = self._lib.pia_align_strands(self._h, n, b"".join(reads), off.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)),
+                                         align.ctypes.data_as(pi), dist.ctypes.data_as(pi), other.ctypes.data_as(pi),
+                                         strand.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)))
+        if rc:
+            raise PwrError(rc, self._lib.pwr_strerror(rc).decode())
+        return [align[off[j]:off[j + 1]].copy() for j in range(n)], dist[:n].copy(), strand[:n].copy(), other[:n].copy()
+
+    def turned(self, reads, strands):
+        """the reads in the orientation align_strands aligned them (pia_turn): reads[j] where strands[j] is 0, its reverse
+        complement where it is 1 -- what build_msa takes next to align_strands' placements"""
+        reads = [_clean(r) for r in reads]
+        n = len(reads)
+        if len(strands) != n:
+            raise ValueError("one strand per read")
+        off = np.zeros(n + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(r) for r in reads])
+        st = np.ascontiguousarray(np.asarray(list(strands) + [0], dtype=np.uint8))
+        out = ctypes.create_string_buffer(max(int(off[-1]), 1))
+        rc = self._lib.pia_turn(n, b"".join(reads), off.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)),
+                                st.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)), out)
+        if rc:
+            raise PwrError(rc, self._lib.pwr_strerror(rc).decode())
+        return [out.raw[off[j]:off[j + 1]] for j in range(n)]
+
     def build_msa(self, msa_path, class_path, reads, placements, distances, cutoff=0.30):
         """Building_MSA (IA:553-663) on alignments from align()."""
         reads = [_clean(r) for r in reads]
@@ -90,8 +129,9 @@ class InitialAligner:
                 "last_align_ms": dict(zip(("total", "upload", "pass1", "pass2_and_traceback", "pass2_batches", "download"), t))}
 
 
-def run_files(template_path, reads_path, msa_path=None, class_path=None, cutoff=None, device=None):
-    """The drop-in binary with the reference's argv (IA:667-735); returns (exit code, stdout lines)."""
+def run_files(template_path, reads_path, msa_path=None, class_path=None, cutoff=None, device=None, strands_path=None):
+    """The drop-in binary with the reference's argv (IA:667-735); returns (exit code, stdout lines).  strands_path: `-b`, reads
+    from either strand; the file gets one line per record, + or -."""
     if not os.path.exists(CLI_PATH):
         raise RuntimeError(f"{CLI_PATH} is missing: build it with `make -C repeatresolver_amd/csrc`")
     cmd = [CLI_PATH, str(template_path), str(reads_path)]
@@ -103,5 +143,7 @@ def run_files(template_path, reads_path, msa_path=None, class_path=None, cutoff=
         cmd += ["-e", repr(float(cutoff))]
     if device is not None:
         cmd += ["-g", str(device)]
+    if strands_path is not None:
+        cmd += ["-b", str(strands_path)]
     p = subprocess.run(cmd, capture_output=True, text=True)
     return p.returncode, p.stdout.splitlines()

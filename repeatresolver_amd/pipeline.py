@@ -9,18 +9,32 @@ import time
 
 from . import datagen as dg
 from .initial_aligner import InitialAligner
+from .strands import seeded_mask, turn
 
 
-def initial_msa(cfg: dg.SimConfig, device: int = 0, cutoff: float = 0.30):
+def initial_msa(cfg: dg.SimConfig, device: int = 0, cutoff: float = 0.30, both_strands: bool = False, reverse_seed=None):
     """Returns (rows, info): rows = the lines of the `<ds>_MSA` file InitialAligner writes for the data set `cfg` describes
-    (reads whose repeat part is shorter than cfg.min_aligned bases are left out: ReadCutter's mapping would not find them)."""
+    (reads whose repeat part is shorter than cfg.min_aligned bases are left out: ReadCutter's mapping would not find them).
+    both_strands: the reads may lie on either strand (InitialAligner.align_strands); info["strands"] is the strand taken per
+    read handed to InitialAligner and info["reverse"] their count.  The simulator only ever samples the template's strand;
+    reverse_seed (an int) hands the reads over as a sequencer would, a seeded half of them as their reverse complement
+    (strands.seeded_mask(len(reads), reverse_seed), info["turned"])."""
     t0 = time.time()
     seq, _full, _starts, _cids, cut, _ = dg.simulate_dataset(cfg)
     templ = dg.ASCII[seq].tobytes()
     reads = [dg.ASCII[r].tobytes() for r in cut if r is not None and len(r) >= cfg.min_aligned]
+    mask = None
+    if reverse_seed is not None:
+        mask = seeded_mask(len(reads), reverse_seed)
+        reads = turn(reads, mask)
     t1 = time.time()
     g = InitialAligner(templ, device=device)
-    place, dist = g.align(reads)
+    strands = None
+    if both_strands:
+        place, dist, strands, _other = g.align_strands(reads)
+        reads = g.turned(reads, strands)
+    else:
+        place, dist = g.align(reads)
     st = g.stats()
     t2 = time.time()
     tmp = tempfile.mkdtemp(prefix="pia_msa_")
@@ -39,14 +53,20 @@ def initial_msa(cfg: dg.SimConfig, device: int = 0, cutoff: float = 0.30):
     info = {"reads": len(reads), "bases": sum(len(r) for r in reads), "template": len(templ), "rows": len(rows),
             "rejected_by_cutoff": classes.count("l"), "cells": st["cells"], "align_ms": st["last_align_ms"],
             "simulate_s": round(t1 - t0, 1), "align_s": round(t2 - t1, 2), "build_msa_s": round(time.time() - t2, 1)}
+    if mask is not None:
+        info["turned"] = mask
+    if strands is not None:
+        info["strands"] = [int(v) for v in strands]
+        info["reverse"] = int(sum(info["strands"]))
     return rows, info
 
 
 def initial_msa_from_reads(cfg: dg.SimConfig, device: int = 0, cutoff: float = 0.30, parts: int = 60, overlap: int = 0,
-                           error_cutoff: float = 0.30):
+                           error_cutoff: float = 0.30, both_strands: bool = False):
     """The reference pipeline's own way in, from the *full* reads (no ground truth): writes the data set's reads FASTA
     (datagen.write_dataset), runs the ReadCutter drop-in on it (GPU), then InitialAligner (GPU) on the Seq.fasta it wrote.
-    Returns (rows, info) like initial_msa."""
+    Returns (rows, info) like initial_msa.  both_strands: ReadCutter looks for its cut points in both orientations of every
+    read (`-b 1`) and InitialAligner takes each piece on the strand it aligns on; info["strands"] is the strand per piece."""
     from .initial_aligner import _clean
     from .read_cutter import run_files
     t0 = time.time()
@@ -58,7 +78,7 @@ def initial_msa_from_reads(cfg: dg.SimConfig, device: int = 0, cutoff: float = 0
         seq_path, rsi_path = os.path.join(tmp, "cut_Seq.fasta"), os.path.join(tmp, "cut_ReadSeqInfo")
         t1 = time.time()
         code, out = run_files(templ_path, os.path.join(tmp, "ds.fasta"), seq_path, rsi_path, parts=parts, overlap=overlap,
-                              error_cutoff=error_cutoff, device=device)
+                              error_cutoff=error_cutoff, device=device, both_strands=both_strands)
         if code != 0:
             raise RuntimeError(f"ReadCutter failed ({code}): {out[-500:]}")
         t2 = time.time()
@@ -67,8 +87,13 @@ def initial_msa_from_reads(cfg: dg.SimConfig, device: int = 0, cutoff: float = 0
         with open(seq_path, "rb") as f:
             reads = [_clean(r) for r in f.read().split(b">")[1:]]
         g = InitialAligner(templ, device=device)
+        strands = None
         try:
-            place, dist = g.align(reads)
+            if both_strands:
+                place, dist, strands, _other = g.align_strands(reads)
+                reads = g.turned(reads, strands)
+            else:
+                place, dist = g.align(reads)
             st = g.stats()
             t3 = time.time()
             msa_path, cls_path = os.path.join(tmp, "MSA"), os.path.join(tmp, "SeqClass")
@@ -86,6 +111,9 @@ def initial_msa_from_reads(cfg: dg.SimConfig, device: int = 0, cutoff: float = 0
     info = {"pieces": len(reads), "bases": sum(len(r) for r in reads), "template": len(templ), "rows": len(rows),
             "rejected_by_cutoff": classes.count("l"), "cells": st["cells"], "write_dataset_s": round(t1 - t0, 1),
             "read_cutter_s": round(t2 - t1, 2), "align_s": round(t3 - t2, 2), "build_msa_s": round(time.time() - t3, 1)}
+    if strands is not None:
+        info["strands"] = [int(v) for v in strands]
+        info["reverse"] = int(sum(info["strands"]))
     return rows, info
 
 

@@ -1,0 +1,303 @@
+"""-m gpu: reads from either strand through InitialAligner (pia_align_strands) and ReadCutter (prc_occurrences_strands,
+prc_cut_strands), the two drop-in binaries with -b, their chain and pipeline.initial_msa.  The yardsticks are the ones the
+forward entries are pinned with -- oracle/libiaoracle.so and rc_checker.py -- applied to each read and to its reverse
+complement made in Python, and composed by strand_checker.py; test_strands.py checks, without a GPU, what the inputs here
+rely on."""
+import ctypes
+import random
+import subprocess
+
+import pytest
+
+import rc_checker as ck
+import strand_checker as sc
+from repeatresolver_amd import initial_aligner, pipeline, read_cutter
+from repeatresolver_amd.initial_aligner import InitialAligner
+from repeatresolver_amd.realigner import PwrError
+from repeatresolver_amd.strands import reverse_complement
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def oracle():
+    return sc.ia_oracle()
+
+
+def _check(templ, reads, oracle, mem_budget=None, expected=None):
+    """align_strands against the oracle on both orientations: strand, both distances, every placement; the cells counted"""
+    g = InitialAligner(templ)
+    try:
+        if mem_budget is not None:
+            g.set_option("mem_budget", mem_budget)
+        place, dist, strand, other = g.align_strands(reads)
+        turned = g.turned(reads, strand)
+        st = g.stats()
+    finally:
+        g.close()
+    assert st["cells"] == 2 * sum(len(r) for r in reads) * len(templ)
+    expected = expected or [sc.align_strands(oracle, r, templ) for r in reads]
+    for j, (r, (s, p, d, o)) in enumerate(zip(reads, expected)):
+        assert (int(strand[j]), int(dist[j]), int(other[j])) == (s, d, o), (j, len(r), len(templ))
+        assert list(place[j]) == p, (j, len(r), len(templ))
+        assert turned[j] == (reverse_complement(r) if s else r)
+    return strand
+
+
+@pytest.mark.parametrize("L2", [1, 31, 32, 33, 2047, 2048, 2049, 4100])
+def test_lane_and_word_boundaries_on_both_strands(L2, oracle):
+    """the read set of test_lane_and_word_boundaries with its three alphabets, every read also as its reverse complement"""
+    rng = random.Random(1000 + L2)
+    nreads = 0
+    for alpha in (b"a", b"ac", b"acgt"):
+        templ_a = bytes(rng.choice(list(alpha)) for _ in range(L2))
+        rs = [b"", b"a", b"t", templ_a[:63], templ_a[-64:], templ_a[L2 // 3:L2 // 3 + 65], templ_a,
+              sc.mutate(rng, templ_a[L2 // 4:L2 // 4 + 300], 0.2), sc.mutate(rng, templ_a, 0.1)[:700],
+              bytes(rng.choice(list(b"acgt")) for _ in range(130)), templ_a[:40] + templ_a[-40:]]
+        reads = rs + [sc.rc(r) for r in rs]
+        strand = _check(templ_a, reads, oracle)
+        nreads += len(reads)
+        if alpha == b"acgt" and L2 >= 2047:
+            assert strand[6] == 0 and strand[11 + 6] == 1              # the template itself, and turned
+    assert nreads == 66
+
+
+def test_reversed_chunk_load(oracle):
+    """exact template substrings around the 64-base chunk, given turned: strand 1, distance 0, consecutive placements"""
+    templ, subs = sc.chunk_case()
+    g = InitialAligner(templ)
+    try:
+        place, dist, strand, other = g.align_strands([sc.rc(s) for _, s in subs])
+    finally:
+        g.close()
+    for j, (a, s) in enumerate(subs):
+        assert (int(strand[j]), int(dist[j])) == (1, 0) and int(other[j]) > 0, len(s)
+        assert list(place[j]) == list(range(a, a + len(s))), len(s)
+
+
+def test_ties_go_to_the_forward_strand(oracle):
+    templ = b"ggcatacgtacgtacgtacgtacgtttgacc"
+    reads = [b"acgt", b"acgt" * 4, b"acgt" * 40, b"a", b"t", b"c", b"g", b"", b"at", b"gc"]
+    assert all(sc.rc(r) == r for r in reads if len(r) != 1)
+    strand = _check(templ, reads, oracle)
+    assert not strand.any()
+    for r in reads:
+        assert oracle(r, templ)[1] == oracle(sc.rc(r), templ)[1]        # ties they are
+
+
+@pytest.fixture(scope="module")
+def batch(oracle):
+    templ, reads, m = sc.batch_case()
+    return templ, reads, m, [sc.align_strands(oracle, r, templ) for r in reads]
+
+
+@pytest.mark.parametrize("budget", [None, 1 << 16, 1])
+def test_batches_of_pass_two_on_both_strands(batch, oracle, budget):
+    """300 reads, a seeded half turned, pass 2 in one batch / in batches of 64 KB / one read per batch: the caller's order"""
+    templ, reads, m, expected = batch
+    strand = _check(templ, reads, oracle, budget, expected)
+    clear = [j for j, (s, p, d, o) in enumerate(expected) if d != o and d / max(len(reads[j]), 1) < 0.30]
+    assert len(clear) > 200 and [int(strand[j]) for j in clear] == [m[j] for j in clear]
+
+
+def test_errors_and_input_forms(oracle):
+    from repeatresolver_amd import _lib
+    lib = _lib.load()
+    PI, PLL = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_longlong)
+    h = ctypes.c_void_p()
+    assert lib.pia_create(ctypes.byref(h), b"ttcaGATtacAGgcaa", 16, 0) == 0
+    try:
+        al, dist, other, st = (ctypes.c_int * 8)(), (ctypes.c_int * 1)(), (ctypes.c_int * 1)(), (ctypes.c_ubyte * 1)()
+        off = (ctypes.c_longlong * 2)(0, 8)
+        assert lib.pia_align_strands(h, 1, b"acg-acgt", off, al, dist, other, st) == -4          # PWR_ERR_INPUT
+        assert lib.pia_align_strands(h, 1, b"acgnacgt", off, al, dist, other, st) == -4
+        assert lib.pia_align_strands(h, 1, b"cTGtaaTC", off, al, dist, other, st) == 0           # mixed case, rc of GAttaCAg
+        assert (st[0], dist[0], list(al)) == (1, 0, list(range(4, 12))) and other[0] > 0
+        assert lib.pia_align_strands(h, 1, b"GAttaCAg", off, al, dist, other, st) == 0
+        assert (st[0], dist[0], list(al)) == (0, 0, list(range(4, 12))) and other[0] > 0
+        assert lib.pia_align_strands(h, 1, b"GAttaCAg", off, al, dist, None, st) == -1           # PWR_ERR_ARG
+        assert lib.pia_align_strands(h, 1, b"GAttaCAg", off, al, dist, other, None) == -1
+        assert lib.pia_align_strands(h, -1, b"GAttaCAg", off, al, dist, other, st) == -1
+        assert lib.pia_align_strands(h, 0, None, off, None, None, None, None) == 0                # nreads = 0
+        long_off = (ctypes.c_longlong * 2)(0, 40001)
+        big = (ctypes.c_int * 40001)()
+        assert lib.pia_align_strands(h, 1, b"a" * 40001, long_off, big, dist, other, st) == -5   # PWR_ERR_RANGE (IA:742)
+    finally:
+        lib.pia_destroy(h)
+    g = InitialAligner(b"acgtacgt")
+    try:
+        with pytest.raises(PwrError) as e:
+            g.align_strands([b"a" * 40001])
+        assert e.value.code == -5
+        place, dist, strand, other = g.align_strands([])
+        assert place == [] and len(dist) == 0 and len(strand) == 0 and len(other) == 0
+        assert g.turned([], []) == []
+    finally:
+        g.close()
+
+
+def test_cli_strand_file(tmp_path):
+    """a seeded half of the records turned: -b names exactly those among the records that pass the cut-off, and the MSA and
+    SeqClass are the files the binary writes without -b for the original reads; without -b nothing is written"""
+    templ, reads, m = sc.cli_case()
+    t, orig, mixed = tmp_path / "x_Template.fasta", tmp_path / "orig_Seq.fasta", tmp_path / "mixed_Seq.fasta"
+    t.write_bytes(b">\n" + templ + b"\n")
+    orig.write_bytes(sc.fasta(reads))
+    mixed.write_bytes(sc.fasta(sc.turn(reads, m)))
+    rc, lines0 = initial_aligner.run_files(t, orig, tmp_path / "msa0", tmp_path / "cls0")
+    assert rc == 0, lines0
+    rc, lines1 = initial_aligner.run_files(t, mixed, tmp_path / "msa1", tmp_path / "cls1", strands_path=tmp_path / "strands")
+    assert rc == 0, lines1
+    classes = (tmp_path / "cls0").read_text().split()
+    assert classes.count("r") == 40 and classes.count("l") == 2
+    strands = (tmp_path / "strands").read_text().split("\n")
+    assert strands[-1] == "" and len(strands) == len(reads) + 1 and set(strands[:-1]) <= {"+", "-"}
+    assert [s for s, c in zip(strands, classes) if c == "r"] == ["-" if v else "+" for v, c in zip(m, classes) if c == "r"]
+    assert [s for s, c in zip(strands, classes) if c == "l"] == ["+", "+"]
+    assert (tmp_path / "cls1").read_bytes() == (tmp_path / "cls0").read_bytes()
+    assert (tmp_path / "msa1").read_bytes() == (tmp_path / "msa0").read_bytes()
+    fix = lambda ls: [l.replace("msa1", "msa0").replace("cls1", "cls0") for l in ls]
+    assert fix(lines1) == lines0                                                                 # the same stdout
+    # forward only, the mixed file loses the turned records
+    rc, _ = initial_aligner.run_files(t, mixed, tmp_path / "msa2", tmp_path / "cls2")
+    assert rc == 0 and (tmp_path / "cls2").read_text().split().count("r") == 40 - sum(v for v, c in zip(m, classes) if c == "r")
+
+
+@pytest.mark.parametrize("ln", [1, 31, 32, 33, 64, 500, 513, 2049])
+def test_occurrences_on_both_strands_equal_checker(ln):
+    """random jobs as in test_occurrences_equal_checker, half of the reads turned"""
+    rng = random.Random(ln)
+    rs = lambda n: "".join(rng.choice("acgt") for _ in range(n))
+    big = ln >= 2049
+    mutate = lambda s, rate: sc.mutate(rng, s.encode(), rate).decode()
+    for parts, overlap in ((3, 0), (3, min(ln - 1, 40))) + (() if big else ((1, 0),)):
+        steps = ln - overlap
+        templ = rs(steps * parts)
+        reads = ["", rs(1), rs(max(ln - 1, 1))]
+        for k in range(3 if big else 10):
+            segs = [rs(rng.randrange(0, max(2, ln // 2)))]
+            for _ in range(rng.randrange(0 if not big else 1, 4)):
+                src = ck.piece(templ, parts, overlap, rng.choice((0, parts - 1))).replace("N", "")
+                segs.append(mutate(src, rng.choice((0.0, 0.05, 0.2, 0.4))))
+                segs.append(rs(rng.randrange(0, ln + 5)))
+            r = "".join(segs)[:ln + 3000 if big else 8 * ln + 2000]
+            reads.append(sc.rc(r) if k & 1 else r)
+        g = read_cutter.ReadCutter(templ.encode())
+        try:
+            got = {e: g.occurrences([r.encode() for r in reads], parts, overlap, e, both_strands=True) for e in (0.30, 0.05)}
+            fwd = g.occurrences([r.encode() for r in reads], parts, overlap, 0.30)
+            st = g.stats()
+        finally:
+            g.close()
+        nq = 2 if parts > 1 else 1
+        assert st["cells"] == 5 * sum(len(r) for r in reads) * ln * nq                         # 2 + 2 + 1 orientations
+        pieces = [ck.piece(templ, parts, overlap, q) for q in ((0, parts - 1) if parts > 1 else (0,))]
+        hits = [0, 0]
+        for j, r in enumerate(reads):
+            for s, seq in enumerate((r, sc.rc(r))):
+                rows = [ck.last_row_myers(pc, seq) for pc in pieces]
+                for e in (0.30, 0.05):
+                    exp = [ck.scan(row, ln, int(ln * e)) for row in rows]
+                    assert [list(map(int, o)) for o in got[e][j][s]] == exp, (ln, parts, overlap, e, len(r), s)
+                hits[s] += sum(len(o) for o in got[0.30][j][s])
+            assert [list(map(int, o)) for o in fwd[j]] == [list(map(int, o)) for o in got[0.30][j][0]]
+        if ln >= 64:
+            assert hits[0] > 0 and hits[1] > 0
+
+
+def test_cuts_on_both_strands_equal_checker():
+    """one to six copies of a 300-base template per read: as they are, turned, and inverted neighbours in one read"""
+    templ, reads = sc.cut_case()
+    g = read_cutter.ReadCutter(templ.encode())
+    try:
+        for parts, overlap, e in sc.CUT_CONFIGS:
+            cuts, nfwd, nrev = g.cut([r.encode() for r in reads], parts, overlap, e, both_strands=True)
+            plain = g.cut([r.encode() for r in reads], parts, overlap, e)
+            for j, r in enumerate(reads):
+                exp = sc.cut_strands(templ, r, parts, overlap, e)
+                assert (list(map(int, cuts[j])), int(nfwd[j]), int(nrev[j])) == exp, (parts, overlap, e, j)
+                assert list(map(int, plain[j])) == ck.cut(templ, r, parts, overlap, e)
+    finally:
+        g.close()
+
+
+def test_overflow_rerun_of_a_reverse_job():
+    """a turned read with 60 hits: more runs below the cutoff than the first launch has room for, on the reverse job"""
+    templ, read = sc.overflow_case()
+    g = read_cutter.ReadCutter(templ.encode())
+    try:
+        got = g.occurrences([read.encode()], 2, 0, 0.30, both_strands=True)[0]
+        cuts, nfwd, nrev = g.cut([read.encode()], 2, 0, 0.30, both_strands=True)
+    finally:
+        g.close()
+    exp = sc.occurrences_strands(templ, read, 2, 0, 0.30)
+    assert len(exp[1][0]) > 20
+    assert [[list(map(int, o)) for o in s] for s in got] == exp
+    assert (list(map(int, cuts[0])), int(nfwd[0]), int(nrev[0])) == sc.cut_strands(templ, read, 2, 0, 0.30)
+
+
+def _chain(tmp_path, tag, templ, reads, both):
+    d = tmp_path / tag
+    d.mkdir()
+    (d / "cTemplate.fasta").write_bytes(b">t\n" + templ.encode() + b"\n")
+    (d / "reads.fasta").write_bytes(sc.fasta(reads, 80))
+    p = subprocess.run([read_cutter.CLI_PATH, "cTemplate.fasta", "reads.fasta", "-o", "out_Seq.fasta", "-r", "out_Info", "-p",
+                        str(sc.CHAIN_PARTS)] + (["-b", "1"] if both else []), cwd=str(d), capture_output=True, text=True)
+    assert p.returncode == 0, p.stdout
+    code, lines = initial_aligner.run_files(d / "cTemplate.fasta", d / "out_Seq.fasta", d / "MSA", d / "SeqClass",
+                                            strands_path=d / "strands" if both else None)
+    assert code == 0, lines
+    return p.stdout, (d / "out_Seq.fasta").read_bytes(), (d / "MSA").read_bytes().split(b"\n")[:-1], d
+
+
+def test_chain_read_cutter_then_initial_aligner_on_both_strands(tmp_path):
+    templ, reads, m = sc.chain_case()
+    out0, seq0, rows0, _ = _chain(tmp_path, "orig", templ, reads, False)
+    out1, seq1, rows1, d1 = _chain(tmp_path, "mixed", templ, sc.turn(reads, m), True)
+    assert len(rows0) > 30 and len(rows0) == seq0.count(b">")                                   # every piece is a row
+    assert sorted(rows1) == sorted(rows0) and rows1 != rows0
+    assert out1 == out0                                                                          # the same stdout
+    # the pieces of a turned read are the original's, turned, in the turned read's order
+    recs = lambda b: [r.replace(b"\n", b"") for r in b.split(b">\n")[1:]]
+    assert sorted(min(r, sc.rc(r)) for r in recs(seq1)) == sorted(min(r, sc.rc(r)) for r in recs(seq0))
+    strands = (d1 / "strands").read_text().split()
+    assert len(strands) == len(rows1) and 0 < strands.count("-") < len(strands)
+    # -b on the original file changes nothing there: no read of it is cut on its reverse strand
+    _, seq2, rows2, _ = _chain(tmp_path, "orig_b", templ, reads, True)
+    assert seq2 == seq0 and rows2 == rows0
+
+
+@pytest.fixture(scope="module")
+def pipeline_case():
+    templ, reads = sc.pipeline_reads()
+    return templ, reads, sc.mask(len(reads), sc.PIPELINE_SEED)
+
+
+def test_pipeline_initial_msa_on_both_strands(pipeline_case):
+    templ, reads, m = pipeline_case
+    cfg = sc.pipeline_config()
+    rows0, info0 = pipeline.initial_msa(cfg)
+    rows1, info1 = pipeline.initial_msa(cfg, both_strands=True, reverse_seed=sc.PIPELINE_SEED)
+    assert info0["reads"] == len(reads) == info1["reads"] and "strands" not in info0
+    assert rows1 == rows0 and len(rows0) == len(reads) - info0["rejected_by_cutoff"] > 20
+    assert info1["turned"] == m and info1["strands"] == m and info1["reverse"] == sum(m)
+    assert info1["cells"] == 2 * info0["cells"]
+    rows2, info2 = pipeline.initial_msa(cfg, both_strands=True)                                 # nothing turned: nothing to take back
+    assert rows2 == rows0 and info2["reverse"] == 0
+
+
+def test_forward_only_loses_the_turned_reads(pipeline_case):
+    """what the feature is for: through `align`, every turned read whose original passes the 0.30 cut-off fails it"""
+    templ, reads, m = pipeline_case
+    g = InitialAligner(templ)
+    try:
+        _, d0 = g.align(reads)
+        _, d1 = g.align(sc.turn(reads, m))
+    finally:
+        g.close()
+    passed = [j for j, r in enumerate(reads) if d0[j] / len(r) < 0.30]
+    assert len(passed) > 20 and sum(m[j] for j in passed) > 10
+    for j in passed:
+        assert (d1[j] / len(reads[j]) < 0.30) == (not m[j]), j
+        if not m[j]:
+            assert d1[j] == d0[j]
