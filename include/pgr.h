@@ -178,6 +178,13 @@ int pgr_kmeans_subdivide_pairs(const pgr_window *win, const pgr_result *refined,
 /* Duration of the last pgr_kmeans_subdivide, ms: [0] all, [1] upload + counts |G & U|, [2] the significance kernel, [3]
  * centroids + assignment + scores, [4] the chain on the host; [5] pairs evaluated.  (Kept per process, not per call.) */
 int pgr_last_kmeans_timing(double *ms6);
+/* Test hooks, not product: the device's tail functions as the group refinement's and the k-means stage's files compile them,
+ * arguments and refusals as pmc_tail_probe (pmc.h).  pgr_tail_probe: out[n][2] = the tail's -log10 with floor[t],
+ * Group_PositiveSignificance (RR:472-488) with floor[t] (size1 = |G_i|, size2 = |G_a|).  pgr_km_tail_probe: out[n][3] =
+ * hypergeometric P(schnitt), Q(schnitt - 1) (0 at schnitt = 0, RR:493), the relative significance (RR:490-504); floor is
+ * not read. */
+int pgr_tail_probe(int n, const int *counts, const double *floor, int device, double *out);
+int pgr_km_tail_probe(int n, const int *counts, const double *floor, int device, double *out);
 
 /* ---- host side, plain C (pgr_host.c) ---- */
 /* The reassignment chain of Kmeans (RR:2726-2755), literally: scores[i * anzahl + j] = GrMatch(Centroids[j], VarSigs[i]),

@@ -30,6 +30,12 @@ int pmc_maxcorrs(int rows, int width, const unsigned char *text, int mincov, int
 /* Duration of the last pmc_maxcorrs' device work, ms: [0] all, [1] bit sets, [2] ranges (MC:801), [3] pairs; [4] pairs evaluated.
  * (Kept per process, not per call: meaningful when pmc_maxcorrs is not called from several threads at once.) */
 int pmc_last_timing(double *ms5);
+/* Test hook, not product: the device's tail functions as the MaxCorrelation kernel's file compiles them, one thread per tuple
+ * counts[n][6] = (schnitt, cov, gr1, gr2, size1, size2); floor[n] (NULL: 0) is the early-out's floor.  out[n][4] =
+ * hypergeometric Q(schnitt - 1), the tail's -log10 with floor 0, with floor[t], PositiveSignificance (MC:413-434) with floor[t].
+ * PWR_ERR_ARG, before anything is launched, for a tuple the pair kernel cannot produce: it needs 0 <= schnitt <=
+ * min(gr1, gr2), max(gr1, gr2) <= cov <= PMC_MAX_ROWS, schnitt >= gr1 + gr2 - cov, gr <= size <= PMC_MAX_ROWS. */
+int pmc_tail_probe(int n, const int *counts, const double *floor, int device, double *out);
 
 /* ---- host side, plain C (pmc_host.c) ---- */
 /* Einlesen (MC:270-336): the first line sets the width, lines of another width are skipped; *text is malloc'ed. */

@@ -35,7 +35,7 @@ PRC_EXPORTS = ["prc_create", "prc_destroy", "prc_occurrences", "prc_cut", "prc_g
                "prc_run_files", "prc_occurrences_strands", "prc_cut_strands", "prc_merge_cuts", "prc_run_files_strands"]
 
 # every symbol include/pmc.h declares (MaxCorrelation)
-PMC_EXPORTS = ["pmc_maxcorrs", "pmc_last_timing", "pmc_read_msa", "pmc_write", "pmc_run_file"]
+PMC_EXPORTS = ["pmc_maxcorrs", "pmc_last_timing", "pmc_read_msa", "pmc_write", "pmc_run_file", "pmc_tail_probe"]
 
 # every symbol include/pgr.h declares (RepeatResolver's group refinement)
 PGR_EXPORTS = ["pgr_refine", "pgr_free", "pgr_last_timing", "pgr_read_window", "pgr_window_free", "pgr_slice_maxcorrs",
@@ -45,7 +45,8 @@ PGR_EXPORTS = ["pgr_refine", "pgr_free", "pgr_last_timing", "pgr_read_window", "
                "pgr_last_kmeans_timing", "pgr_kmeans_reassign", "pgr_msa_open", "pgr_msa_close", "pgr_msa_window", "pgr_msa_resolve",
                "pgr_resolution_free", "pgr_last_resolve_timing", "pgr_connect", "pgr_connection_free", "pgr_msa_consensus",
                "pgr_consensus_free", "pgr_last_consensus_timing", "pgr_resolvability", "pgr_msa_assign", "pgr_assignment_free",
-               "pgr_last_assign_timing", "pgr_msa_settle", "pgr_settlement_free", "pgr_last_settle_timing"]
+               "pgr_last_assign_timing", "pgr_msa_settle", "pgr_settlement_free", "pgr_last_settle_timing", "pgr_tail_probe",
+               "pgr_km_tail_probe"]
 
 # constants of include/pgr.h that tests and scripts cite (pgr_cons_device.hip)
 PGR_MAX_ROWS = 30000
@@ -357,5 +358,8 @@ def load():
     lib.pgr_settlement_free.argtypes = [ctypes.POINTER(PgrSettlement)]
     lib.pgr_last_settle_timing.restype = ci
     lib.pgr_last_settle_timing.argtypes = [pd]
+    for n in ("pmc_tail_probe", "pgr_tail_probe", "pgr_km_tail_probe"):   # test hooks (tail_probe.py)
+        getattr(lib, n).restype = ci
+        getattr(lib, n).argtypes = [ci, pi, pd, ci, pd]
     _lib = lib
     return lib

@@ -102,4 +102,46 @@ __device__ __forceinline__ double d_hyper_sum(const double *__restrict__ lnf, un
     return lnf;
 }
 
+// What the three stages' callers can hand to the functions above, for the test hooks (p*_tail_probe) that evaluate them on
+// chosen counts: n tuples (schnitt, cov, gr1, gr2, size1, size2).  The lnf lookups have no bounds check of their own; inside
+// these inequalities every index is a count between 0 and cov.  *maxcov: the largest cov, what the table has to reach.
+[[maybe_unused]] static bool hyper_probe_counts_ok(int n, const int *counts, int max_rows, int *maxcov)
+{
+    if (n <= 0 || n > (1 << 24) || !counts) return false;
+    int mc = 0;
+    for (int t = 0; t < n; ++t) {
+        const int *c = counts + (size_t)t * 6;
+        const int s = c[0], cov = c[1], g1 = c[2], g2 = c[3], z1 = c[4], z2 = c[5];
+        if (s < 0 || g1 < 0 || g2 < 0 || s > g1 || s > g2) return false;               // 0 <= schnitt <= min(gr1, gr2)
+        if (cov > max_rows || g1 > cov || g2 > cov) return false;                      // max(gr1, gr2) <= cov <= rows
+        if ((long long)s < (long long)g1 + g2 - cov) return false;                     // the two groups fit into cov rows
+        if (z1 < g1 || z2 < g2 || z1 > max_rows || z2 > max_rows) return false;        // gr <= size <= rows
+        if (cov > mc) mc = cov;
+    }
+    *maxcov = mc;
+    return true;
+}
+
+// The host side of a test hook: refuses before any launch what hyper_probe_counts_ok refuses, builds the table as the stages
+// do, and hands the device copies to `launch(n, counts, floor or null, lnf, out)`, the including file's own probe kernel
+// (one thread per tuple, nout doubles each) -- compiled with that file's flags, which is the point.  Needs dev_util.h.
+template <class Launch>
+static int hyper_probe_run(int n, const int *counts, const double *floor, int device, int max_rows, int nout, double *out, Launch launch)
+{
+    int maxcov = 0;
+    if (!out || !hyper_probe_counts_ok(n, counts, max_rows, &maxcov)) return PWR_ERR_ARG;
+    if (hipSetDevice(device) != hipSuccess) return PWR_ERR_DEVICE;
+    const std::vector<double> lnf = hyper_lnf_table(maxcov);
+    DevArena dev;
+    const int *d_counts = dev.put(counts, (size_t)n * 6);
+    const double *d_floor = floor ? dev.put(floor, (size_t)n) : nullptr;
+    const double *d_lnf = dev.put(lnf.data(), lnf.size());
+    double *d_out = dev.get<double>((size_t)n * nout);
+    if (!d_counts || (floor && !d_floor) || !d_lnf || !d_out) return dev.err;
+    launch(n, d_counts, d_floor, d_lnf, d_out);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpy(out, d_out, (size_t)n * nout * sizeof(double), hipMemcpyDeviceToHost));
+    return PWR_OK;
+}
+
 #endif /* PWR_HYPER_TAIL_H */

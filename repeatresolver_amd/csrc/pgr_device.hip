@@ -50,6 +50,11 @@ __device__ __forceinline__ bool better(double z1, int i1, double z2, int i2)
 // RR:472-488 Group_PositiveSignificance(G_i, G_a, LC_i, LC_a) from the four counts and the two group sizes: d_tail_z
 // (hyper_tail.h) and this stage's saturated value.  `floor`: what a value has to reach to matter (greedy, or the 29th of
 // the running list).
+// The counts k_gr_cliques hands over stay inside what the table covers (hyper_probe_counts_ok states the inequalities): the
+// window reader sets a row's bit in a group and in its column's coverage together, so every G is a subset of its LC; with
+// C = LC_i & LC_a (cov rows, cov <= kept rows = the table's reach), gr1 = |G_i & LC_a| and gr2 = |G_a & LC_i| count
+// subsets of C whose intersection is G_i & G_a: schnitt <= min(gr1, gr2), gr1 + gr2 - schnitt = |union| <= cov; the sizes
+// are |G_i| >= gr1 and |G_a| >= gr2 (gsize is the popcount of the same sets).
 __device__ __forceinline__ double d_gr_significance(const double *__restrict__ lnf, int schnitt, int cov, int gr1, int gr2, int size_i, int size_a, double floor)
 {
     double Z = d_tail_z(lnf, schnitt, cov, gr1, gr2, floor);                                   // RR:451-453
@@ -445,6 +450,27 @@ int pgr_refine_sets(const pgr_device_sets *sets, const unsigned char *kept, cons
     if (rc) { pgr_free(result); return rc; }
     if (ms2) { ms2[0] = ms[0]; ms2[1] = ms[1]; }
     return PWR_OK;
+}
+
+// ---- test hook: the tail functions k_gr_cliques calls, as this file compiles them, on given counts (thread = one tuple) ----
+__global__ __launch_bounds__(256) void k_gr_tail_probe(int n, const int *__restrict__ counts, const double *__restrict__ floor,
+                                                       const double *__restrict__ lnf, double *__restrict__ out)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const int *c = counts + (size_t)t * 6;
+    const double fl = floor ? floor[t] : 0.0;
+    out[(size_t)t * 2] = d_tail_z(lnf, c[0], c[1], c[2], c[3], fl);
+    out[(size_t)t * 2 + 1] = d_gr_significance(lnf, c[0], c[1], c[2], c[3], c[4], c[5], fl);
+}
+
+extern "C" int pgr_tail_probe(int n, const int *counts, const double *floor, int device, double *out)
+{
+    return abi_guard([&] {
+        return hyper_probe_run(n, counts, floor, device, PGR_MAX_ROWS, 2, out, [](int m, const int *c, const double *f, const double *l, double *o) {
+            hipLaunchKernelGGL(k_gr_tail_probe, dim3((m + 255) / 256), dim3(256), 0, 0, m, c, f, l, o);
+        });
+    });
 }
 
 // ---- the drop-off subdivisions (RR:4026-4062) ----

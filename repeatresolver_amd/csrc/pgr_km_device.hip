@@ -63,6 +63,11 @@ __global__ __launch_bounds__(PKM_NT) void k_km_counts(int nC, int sc, const u64 
 }
 
 // RR:506-522 with CumHypGeo_Log (RR:490-504) from the counts
+// The counts k_km_pairs hands over stay inside what the table covers (hyper_probe_counts_ok states the inequalities): cov is
+// the number of rows of the part U_e (at most the kept rows, the table's reach), gr1 and gr2 are |G & U_e| of the two
+// variations (k_km_counts), subsets of U_e, and schnitt = |G_a & G_b & U_e| is the size of their intersection:
+// schnitt <= min(gr1, gr2) and gr1 + gr2 - schnitt = |union| <= cov.  At schnitt == 0 the Q side gets k = 2^32 - 1, which
+// d_hyper_Q answers with 0 before any lookup (k >= n1).
 __device__ __noinline__ double d_km_significance(const double *__restrict__ lnf, int schnitt, int cov, int gr1, int gr2)
 {
     if (gr1 == 0 || gr2 == 0) return 0.0;
@@ -476,6 +481,28 @@ static int kmeans_checked(const pgr_window *win, const pgr_result *refined, cons
     const int rc = abi_guard([&] { return kmeans(win, refined, labels_rows, mincov, device, want_pairs, out); });
     if (rc) pgr_kmeans_free(out);
     return rc;
+}
+
+// ---- test hook: the tail functions k_km_pairs calls, as this file compiles them, on given counts (thread = one tuple) ----
+__global__ __launch_bounds__(256) void k_km_tail_probe(int n, const int *__restrict__ counts, const double *__restrict__ lnf, double *__restrict__ out)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const int *c = counts + (size_t)t * 6;
+    const int s = c[0], cov = c[1], g1 = c[2], g2 = c[3];
+    double *o = out + (size_t)t * 3;
+    o[0] = d_hyper_P(lnf, (unsigned)s, (unsigned)g2, (unsigned)(cov - g2), (unsigned)g1);
+    o[1] = d_hyper_Q(lnf, (unsigned)s - 1u, (unsigned)g2, (unsigned)(cov - g2), (unsigned)g1);
+    o[2] = d_km_significance(lnf, s, cov, g1, g2);
+}
+
+extern "C" int pgr_km_tail_probe(int n, const int *counts, const double *floor, int device, double *out)
+{
+    return abi_guard([&] {
+        return hyper_probe_run(n, counts, floor, device, PGR_MAX_ROWS, 3, out, [](int m, const int *c, const double *, const double *l, double *o) {
+            hipLaunchKernelGGL(k_km_tail_probe, dim3((m + 255) / 256), dim3(256), 0, 0, m, c, l, o);
+        });
+    });
 }
 
 extern "C" int pgr_kmeans_subdivide(const pgr_window *win, const pgr_result *refined, const int *reldrop_labels_rows, int mincov, int device,

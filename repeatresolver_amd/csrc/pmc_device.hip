@@ -140,6 +140,10 @@ __global__ __launch_bounds__(256) void k_mc_end(int W, int sc, int mincov, const
 // `floor`: what the two maxima this pair could raise already hold: a pair that cannot raise either maximum is dropped before
 // the sum (after a few thousand partners every variation's maximum is past what chance co-occurrence reaches, and almost
 // every pair ends here -- the sums took 93 % of the kernel before).
+// The counts k_mc_pairs hands over stay inside what the table covers (hyper_probe_counts_ok states the inequalities): with
+// C = LC_i & LC_j (cov rows, cov <= T = the table's reach), gr1 = |G_i & LC_j| and gr2 = |G_j & LC_i| count subsets of C
+// because k_mc_bits makes every G a subset of its column's LC; schnitt = |G_i & G_j| is the size of their intersection,
+// so schnitt <= min(gr1, gr2) and gr1 + gr2 - schnitt = |union| <= cov; size1 = |G_i| >= gr1, size2 = |G_j| >= gr2.
 __device__ __forceinline__ double d_significance(const double *__restrict__ lnf, int schnitt, int cov, int gr1, int gr2, int size1, int size2, double floor)
 {
     double Z = d_tail_z(lnf, schnitt, cov, gr1, gr2, floor);
@@ -302,4 +306,29 @@ static int maxcorrs_on_device(int T, int W, const unsigned char *text, int minco
 extern "C" int pmc_maxcorrs(int T, int W, const unsigned char *text, int mincov, int device, double *maxcorrs)
 {
     return abi_guard([&] { return maxcorrs_on_device(T, W, text, mincov, device, maxcorrs); });
+}
+
+// ---- test hook: the tail functions k_mc_pairs calls, as this file compiles them, on given counts (thread = one tuple) ----
+__global__ __launch_bounds__(256) void k_mc_tail_probe(int n, const int *__restrict__ counts, const double *__restrict__ floor,
+                                                       const double *__restrict__ lnf, double *__restrict__ out)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const int *c = counts + (size_t)t * 6;
+    const int s = c[0], cov = c[1], g1 = c[2], g2 = c[3];
+    const double fl = floor ? floor[t] : 0.0;
+    double *o = out + (size_t)t * 4;
+    o[0] = d_hyper_Q(lnf, (unsigned)(s - 1), (unsigned)g2, (unsigned)(cov - g2), (unsigned)g1);
+    o[1] = d_tail_z(lnf, s, cov, g1, g2, 0.0);
+    o[2] = d_tail_z(lnf, s, cov, g1, g2, fl);
+    o[3] = d_significance(lnf, s, cov, g1, g2, c[4], c[5], fl);
+}
+
+extern "C" int pmc_tail_probe(int n, const int *counts, const double *floor, int device, double *out)
+{
+    return abi_guard([&] {
+        return hyper_probe_run(n, counts, floor, device, PMC_MAX_ROWS, 4, out, [](int m, const int *c, const double *f, const double *l, double *o) {
+            hipLaunchKernelGGL(k_mc_tail_probe, dim3((m + 255) / 256), dim3(256), 0, 0, m, c, f, l, o);
+        });
+    });
 }
