@@ -803,6 +803,7 @@ __device__ __forceinline__ unsigned acc_push(unsigned acc, unsigned long long ma
     return acc;
 }
 #define ICMP_SGE 39
+#define ICMP_SLT 40
 #define ICMP_SLE 41
 
 // records of macro-strip MSX: the four substitution columns S_b - G go to this wave's LDS table SLOT (read back
@@ -1266,6 +1267,9 @@ __global__ __launch_bounds__(NW * 64) void k_fill_v2(DState st, JobBufs jb)   //
 // neighbour by one poll of the fetcher (a few DP rows), and the L2 round trip is never on its critical path.
 // Ring words keep their row tags, so an old occupant of a slot is never mistaken for the row in demand.
 // ---------------------------------------------------------------------------------------------
+#ifndef PWR_DIAG_SEG
+#define PWR_DIAG_SEG 0              // (-DPWR_DIAG builds: the segment of job 0 whose waves fill the counters and logs; the last one if there are fewer)
+#endif
 #ifndef PWR_INTERIOR_CLS
 #define PWR_INTERIOR_CLS 0          // (4: interior groups run the RIGHT code, experiment on the effect of equal speeds)
 #endif
@@ -1481,6 +1485,7 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
 
     DG_DECL
 #ifdef PWR_DIAG
+    const bool dg_me = sd->s == min(PWR_DIAG_SEG, UNI(m->nseg) - 1);             // the per-wave counters and logs are one segment's (the time line below is every segment's)
     unsigned long long *const tl = jb.diag + ((size_t)job * 32 + 31) * 4096 + (size_t)(sd->s * NW + wave) * 6;   // the segment's time line
     if (lane == 0 && sd->s * NW + wave < 680) { tl[0] = t_real0; tl[1] = __builtin_amdgcn_s_memrealtime(); tl[2] = 0; }
 #endif
@@ -1560,7 +1565,7 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
                     }
                     DG_ADD(dg_wait_gen)
 #ifdef PWR_DIAG
-                    if (lane == 0 && dg_general < 36) {
+                    if (lane == 0 && dg_me && dg_general < 36) {
                         unsigned long long *ev = jb.diag + ((size_t)job * 32 + wave) * 4096 + 16 + 3 * dg_general;
                         ev[0] = (unsigned long long)x; ev[1] = ev_t0; ev[2] = __builtin_amdgcn_s_memrealtime();
                     }
@@ -1653,50 +1658,119 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
                         g_cs = __builtin_amdgcn_ds_bpermute(src, (int)dcs);
                         g_cp = g0;
                     }
+                    // The scan is six v_min_i32_dpp, each reading the register the one before it wrote: a DPP operand needs two wait
+                    // states behind the VALU write, and where nothing stands between two steps the compiler pads with an s_nop --
+                    // which takes a lone wave's issue slot like any instruction.  So the row's own work that does not depend on the
+                    // scan is dealt out over the six gaps, two instructions or more each, pinned by scheduling fences: the ring
+                    // read, the next row's substitution scores (address, then the reads), the tag, the C bits of a row with record
+                    // (d and u stay live for them; a v_cmp and the v_addc that takes its mask stand a scan step apart, the same two
+                    // wait states), and the band guard of the NEXT row -- its compares depend on the descriptor alone, so their masks
+                    // are made a row ahead and wait in scalar registers (gd[]; guard_head makes them for a stretch's first row).
+                    // Pure scheduling: every register holds what it held.
+                    unsigned long long gd[C];
+#pragma unroll
+                    for (int i = 0; i < C; ++i) gd[i] = ~0ull;
+                    auto guard_head = [&](const int r, auto cls_) __attribute__((always_inline)) {
+                        constexpr int CLS = decltype(cls_)::value;
+                        if (CLS == 1 || CLS == 2 || CLS == 4) {
+                            const int e_ = __builtin_amdgcn_readlane(CLS == 2 ? g_af : g_be, r);
+#pragma unroll
+                            for (int i = 0; i < C; ++i) gd[i] = __builtin_amdgcn_sicmp(ycol[i], e_, CLS == 2 ? ICMP_SGE : ICMP_SLT);
+                        }
+                    };
                     auto group_row = [&](const int r, auto cls_, auto bits_) __attribute__((always_inline)) {
                         constexpr int CLS = decltype(cls_)::value;                 // 0 INTERIOR, 1 RIGHT, 2 LEFT, 3 run-time flags
                         constexpr bool BITS = decltype(bits_)::value;              // false: a row of the warm-up, whose record nobody keeps
+                        constexpr bool AHEAD = CLS == 1 || CLS == 2 || CLS == 4;   // one guard, its masks made a row ahead (gd)
+                        constexpr int CH = (C + 1) / 2;                            // the cells' fillers come in two halves: [0, CH) and [CH, C)
                         bool bP = CLS <= 1 || CLS == 4, bM = CLS <= 1 || CLS == 4;
                         if (CLS == 3) { bP = (nPm >> r) & 1u; bM = (kMm >> r) & 1u; }
                         int af = 0, bend = 0;
-                        if (CLS >= 2) af = __builtin_amdgcn_readlane(g_af, r);
-                        if (CLS == 1 || CLS == 3 || CLS == 4) bend = __builtin_amdgcn_readlane(g_be, r);
+                        if (CLS == 3) { af = __builtin_amdgcn_readlane(g_af, r); bend = __builtin_amdgcn_readlane(g_be, r); }
                         const int Mleft_v = bM ? (int)mlast_v : (int)PWR_INF - gleft;
                         const int pm1_0 = __builtin_amdgcn_update_dpp(Mleft_v, (int)Mprev[C - 1], DPP_WAVE_SHR1, 0xF, 0xF, false);
-                        int tg[C];
+                        int tg[C], dq[C], uq[C];
                         int run = FBIG;
 #pragma unroll
                         for (int i = 0; i < C; ++i) {
                             const int pm1 = i ? (int)Mprev[i > 0 ? i - 1 : 0] : pm1_0;
                             const int d = pm1 + sgr[i];
                             const int u = (int)Mprev[i] + ug[i];
-                            if (BITS) accC[i] = acc_push(accC[i], __builtin_amdgcn_sicmp(d, u, ICMP_SLE));
+                            dq[i] = d; uq[i] = u;
                             const int t3 = min(min(d, u), ig[i]);
                             bool inb = true;
-                            if (CLS == 1 || CLS == 4) inb = ycol[i] < bend;
-                            if (CLS == 2) inb = ycol[i] >= af;
+                            if (AHEAD) inb = __builtin_amdgcn_inverse_ballot_w64(gd[i]);
                             if (CLS == 3) inb = (unsigned)(ycol[i] - af) < (unsigned)(bend - af);
                             tg[i] = inb ? t3 : FBIG;
                             run = min(run, tg[i]);
                         }
-                        // the neighbour's word of this row, from the ring: value and tag in one 64-bit read
-                        unsigned long long fP = 0;
-                        if (CLS != 2) fP = LLD(ringP[r]);
-                        __builtin_amdgcn_sched_barrier(0);
+                        unsigned long long fP = 0, cm[C];
+                        unsigned tagx = 0;
+                        int gb = 0, soff = 0;
+                        const int *srow = nullptr;
 #define V4_SCAN_STEP(CTRL, RMASK) { const int t_ = __builtin_amdgcn_update_dpp(PWR_BIG, incl, CTRL, RMASK, 0xF, false); incl = min(incl, t_); }
 #define V4_FENCE() __builtin_amdgcn_sched_barrier(0)
+                        // the fillers, each pinned where it stands; a VALU that reads a scalar register stands two instructions behind
+                        // the VALU that wrote it (v_readlane -> address, v_cmp -> v_addc / v_cndmask), and two v_addc are not neighbours
+#define V4_F_RING() { fP = LLD(ringP[r]); V4_FENCE(); }                                           /* the neighbour's word of this row: value and tag in one 64-bit read */
+#define V4_F_SOFF() { soff = __builtin_amdgcn_readlane(g_cs, r + 1); V4_FENCE(); }                /* (past the block's end: reloaded below) */
+#define V4_F_EDGE() { if (AHEAD) { gb = __builtin_amdgcn_readlane(CLS == 2 ? g_af : g_be, r + 1); V4_FENCE(); } }
+#define V4_F_TAG()  { tagx = tag_g0 + (unsigned)(r + 1); if (CLS == 2) asm volatile("" :: "s"(tagx)); V4_FENCE(); }   /* (LEFT: only the store wants it, and the compiler would move it there) */                            /* = tagbase | (xr + 1): g0 is a multiple of 16 */
+#define V4_F_SROW() { srow = (const int *)(stab + soff); V4_FENCE(); }
+#define V4_F_SGR(LO, HI) { _Pragma("unroll") for (int i = 0; i < C; ++i) if (i >= (LO) && i < (HI)) sgr[i] = srow[i]; V4_FENCE(); }
+#define V4_F_CC(I)  { if ((I) < C) { cm[(I) < C ? (I) : 0] = __builtin_amdgcn_sicmp(dq[(I) < C ? (I) : 0], uq[(I) < C ? (I) : 0], ICMP_SLE); V4_FENCE(); } }
+#define V4_F_CP(I)  { if ((I) < C) { accC[(I) < C ? (I) : 0] = acc_push(accC[(I) < C ? (I) : 0], cm[(I) < C ? (I) : 0]); V4_FENCE(); } }
+#define V4_F_GD(I)  { if (AHEAD && (I) < C) { gd[(I) < C ? (I) : 0] = __builtin_amdgcn_sicmp(ycol[(I) < C ? (I) : 0], gb, CLS == 2 ? ICMP_SGE : ICMP_SLT); V4_FENCE(); } }
+#define V4_F_BIG()  { asm volatile("" : "+v"(big)); V4_FENCE(); }                                  /* the last step's neutral element, in its register two instructions ahead of the step */
+                        int big = PWR_BIG;
+                        auto gap = [&](auto k_) __attribute__((always_inline)) {
+                            constexpr int K = decltype(k_)::value + (CLS == 2 ? 1 : 0);   // (LEFT reads no ring: its list starts with the second gap's)
+                            if constexpr (decltype(k_)::value == 5 && CLS != 2) V4_F_BIG()   // (LEFT has no branch behind the scan: its last step is one v_min_i32_dpp as it stands)
+                            if constexpr (K == 0) V4_F_RING()
+                            if constexpr (!BITS && AHEAD) {
+                                if constexpr (K == 1) { V4_F_SOFF() V4_F_EDGE() }
+                                if constexpr (K == 2) { V4_F_SROW() V4_F_TAG() }
+                                if constexpr (K == 3) { V4_F_SGR(0, CH) V4_F_SGR(CH, C) }
+                                if constexpr (K == 4) { _Pragma("unroll") for (int i = 0; i < CH; ++i) V4_F_GD(i) }
+                                if constexpr (K == 5) { _Pragma("unroll") for (int i = CH; i < C; ++i) V4_F_GD(i) }
+                            }
+                            if constexpr (!BITS && !AHEAD) {
+                                if constexpr (K == 1) { V4_F_SOFF() V4_F_TAG() }
+                                if constexpr (K == 2) { V4_F_SROW() V4_F_SGR(0, CH) }
+                                if constexpr (K == 3) { V4_F_SGR(CH, C) }
+                            }
+                            if constexpr (BITS) {
+                                // (the instruction behind a v_addc is never a compare: the compiler takes an inline asm's results for
+                                // hazardous to whatever touches their registers next, and a compare likes the carry's scalar pair)
+                                if constexpr (K == 1) { V4_F_SOFF() V4_F_EDGE() }
+                                if constexpr (K == 2) { V4_F_SROW() V4_F_SGR(0, CH) }
+                                if constexpr (K == 3) { _Pragma("unroll") for (int i = 0; i < C - 1; ++i) V4_F_CC(i) }
+                                if constexpr (K == 4) { V4_F_CC(C - 1) _Pragma("unroll") for (int i = 0; i < CH; ++i) { V4_F_CP(i) if (i == 0) V4_F_SGR(CH, C) } }
+                                if constexpr (K == 5) { _Pragma("unroll") for (int i = CH; i < C; ++i) { V4_F_CP(i) if (i == CH) { V4_F_TAG() V4_F_GD(0) } } if (CH == C) { V4_F_TAG() V4_F_GD(0) } }
+                                if constexpr (K == 6) { _Pragma("unroll") for (int i = 1; i < CH; ++i) V4_F_GD(i) }
+                                if constexpr (K == 7) { _Pragma("unroll") for (int i = CH; i < C; ++i) V4_F_GD(i) }
+                            }
+                        };
+                        using std::integral_constant;
                         int incl = run;
-                        V4_SCAN_STEP(DPP_ROW_SHR(1), 0xF) V4_FENCE();
-                        const int soff = __builtin_amdgcn_readlane(g_cs, r + 1);                      // (past the block's end: reloaded below)
-                        V4_FENCE(); V4_SCAN_STEP(DPP_ROW_SHR(2), 0xF) V4_FENCE();
-                        const int *const srow = (const int *)(stab + soff);
-                        V4_FENCE(); V4_SCAN_STEP(DPP_ROW_SHR(4), 0xF) V4_FENCE();
-#pragma unroll
-                        for (int i = 0; i < C; ++i) sgr[i] = srow[i];
-                        V4_FENCE(); V4_SCAN_STEP(DPP_ROW_SHR(8), 0xF) V4_FENCE();
-                        const unsigned tagx = tag_g0 + (unsigned)(r + 1);            // = tagbase | (xr + 1): g0 is a multiple of 16
-                        V4_FENCE(); V4_SCAN_STEP(DPP_ROW_BCAST15, 0xA) V4_FENCE();
-                        V4_FENCE(); V4_SCAN_STEP(DPP_ROW_BCAST31, 0xC) V4_FENCE();
+                        V4_FENCE(); gap(integral_constant<int, 0>{}); V4_SCAN_STEP(DPP_ROW_SHR(1), 0xF) V4_FENCE();
+                        gap(integral_constant<int, 1>{}); V4_SCAN_STEP(DPP_ROW_SHR(2), 0xF) V4_FENCE();
+                        gap(integral_constant<int, 2>{}); V4_SCAN_STEP(DPP_ROW_SHR(4), 0xF) V4_FENCE();
+                        gap(integral_constant<int, 3>{}); V4_SCAN_STEP(DPP_ROW_SHR(8), 0xF) V4_FENCE();
+                        gap(integral_constant<int, 4>{}); V4_SCAN_STEP(DPP_ROW_BCAST15, 0xA) V4_FENCE();
+                        gap(integral_constant<int, 5>{});
+                        { const int t_ = __builtin_amdgcn_update_dpp(big, incl, DPP_ROW_BCAST31, 0xC, 0xF, false); incl = min(incl, t_); } V4_FENCE();
+                        gap(integral_constant<int, 6>{}); gap(integral_constant<int, 7>{});   // (what is left of the longest lists)
+#undef V4_F_BIG
+#undef V4_F_RING
+#undef V4_F_SOFF
+#undef V4_F_EDGE
+#undef V4_F_TAG
+#undef V4_F_SROW
+#undef V4_F_SGR
+#undef V4_F_CC
+#undef V4_F_CP
+#undef V4_F_GD
 #undef V4_SCAN_STEP
 #undef V4_FENCE
                         if (bP && __builtin_expect(UNI(TAGOF(fP)) != tagx, 0)) {
@@ -1718,12 +1792,18 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
                         const int P_in_v = bP ? (int)(unsigned)fP : PWR_BIG;
                         const int P_end_v = min(P_in_v, incl);
                         const int pq = min(P_in_v, FBIG);
+                        // (the word to publish is put together here, not inside the one-lane store: its two instructions are the wait
+                        // states between the scan's result and the shift that reads it)
+                        typedef unsigned v2u_ __attribute__((ext_vector_type(2)));
+                        v2u_ w2_; w2_.x = (unsigned)P_end_v; w2_.y = tagx;
+                        if (!WG1 && CLS != 2) asm volatile("" : "+v"(w2_));        // (LEFT publishes the scan's result as it stands: pinning the pair would cost it a move)
                         int p = min(__builtin_amdgcn_update_dpp(pq, incl, DPP_WAVE_SHR1, 0xF, 0xF, false), pq);
 #pragma unroll
                         for (int i = 0; i < C; ++i) {
                             if (BITS) accA[i] = acc_push(accA[i], __builtin_amdgcn_sicmp(tg[i], p, ICMP_SGE));
                             p = min(p, tg[i]);
                             // N = p: no band guard, so p <= tg[i] <= ig[i] already; behind a guard tg[i] may be FBIG
+                            // (a RIGHT row without its clamp was measured and is NOT in the code: no proof for rows with blank runs)
                             Mprev[i] = (unsigned)(CLS == 0 ? p : min(p, ig[i]));
                         }
                         mlast_v = (unsigned)fP;                                     // M_last(x) = P_end(x) wherever the next row reads it
@@ -1732,8 +1812,6 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
                                 GST2(gq0 + r, P_end_v, tagx);
                                 LST(rP[wr][(g0 + r) & (RB - 1)], ((unsigned long long)tagx << 32) | (unsigned)P_end_v);
                             } else {
-                                typedef unsigned v2u_ __attribute__((ext_vector_type(2)));
-                                v2u_ w2_; w2_.x = (unsigned)P_end_v; w2_.y = tagx;
                                 // (sc1 as the agent-scope atomic stores have it: the word must be seen by the other work-groups; a store
                                 // of 64 bits needs no wait states before a VALU overwrites its data registers)
                                 // (the group's base is wave-uniform: scalar base + the row's byte offset, one move instead of 64-bit address arithmetic)
@@ -1755,18 +1833,22 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
                         // whole groups of the warm-up -- seven rows in ten of a segment --, one role: the same straight-line code without
                         // the two compare-and-shift pairs per cell that make the record
                         if (cls == 0) {
+                            guard_head(0, std::integral_constant<int, PWR_INTERIOR_CLS>{});
 #pragma unroll
                             for (int r = 0; r < 16; ++r) group_row(r, std::integral_constant<int, PWR_INTERIOR_CLS>{}, NoBits{});
                             DG_INC(dg_int, 16)
                             DG_ADD2(dg_cyc_int)
                         } else if (cls == 1) {
+                            guard_head(0, std::integral_constant<int, 1>{});
 #pragma unroll
                             for (int r = 0; r < 16; ++r) group_row(r, std::integral_constant<int, 1>{}, NoBits{});
                         } else {
+                            guard_head(0, std::integral_constant<int, 2>{});
 #pragma unroll
                             for (int r = 0; r < 16; ++r) group_row(r, std::integral_constant<int, 2>{}, NoBits{});
                         }
                     } else if (cls == 0 && r_beg == 0 && r_e == 16) {
+                        guard_head(0, std::integral_constant<int, PWR_INTERIOR_CLS>{});
 #pragma unroll
                         for (int r = 0; r < 16; ++r) group_row(r, std::integral_constant<int, PWR_INTERIOR_CLS>{}, WithBits{});
                         DG_INC(dg_int, 16)
@@ -1774,6 +1856,7 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
                     } else if (cls == 1 && r_beg == 0 && r_e == 16) {
                         // (the band's last strip: its wave has just taken it over and the next strip's wave is waiting for it --
                         // this is the pipeline's critical path, so whole groups get straight-line code here too)
+                        guard_head(0, std::integral_constant<int, 1>{});
 #pragma unroll
                         for (int r = 0; r < 16; ++r) group_row(r, std::integral_constant<int, 1>{}, WithBits{});
                     } else if (cls == 3 && r_beg == 0 && r_e == 16) {
@@ -1781,16 +1864,17 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
                         for (int r = 0; r < 16; ++r) group_row(r, std::integral_constant<int, 3>{}, WithBits{});
                     } else if (cls == 2 && r_beg == 0 && r_e == 16) {
                         // (the band's first strip: with every follower close behind its neighbour, its rows set the pace)
+                        guard_head(0, std::integral_constant<int, 2>{});
 #pragma unroll
                         for (int r = 0; r < 16; ++r) group_row(r, std::integral_constant<int, 2>{}, WithBits{});
                     } else {
                         int r = r_beg;
                         for (; r < r_end && (r & 3) && !dead; ++r) group_row(r, std::integral_constant<int, 3>{}, WithBits{});
-#define V4_BLOCKS(K) for (; r + 4 <= r_end && !dead; r += 4) { group_row(r, std::integral_constant<int, K>{}, WithBits{}); group_row(r + 1, std::integral_constant<int, K>{}, WithBits{}); \
+#define V4_BLOCKS(K) guard_head(r, std::integral_constant<int, K>{}); for (; r + 4 <= r_end && !dead; r += 4) { group_row(r, std::integral_constant<int, K>{}, WithBits{}); group_row(r + 1, std::integral_constant<int, K>{}, WithBits{}); \
                                                                group_row(r + 2, std::integral_constant<int, K>{}, WithBits{}); group_row(r + 3, std::integral_constant<int, K>{}, WithBits{}); }
-                        if (cls == 0) V4_BLOCKS(0)
-                        else if (cls == 1) V4_BLOCKS(1)
-                        else if (cls == 2) V4_BLOCKS(2)
+                        if (cls == 0) { V4_BLOCKS(0) }
+                        else if (cls == 1) { V4_BLOCKS(1) }
+                        else if (cls == 2) { V4_BLOCKS(2) }
 #undef V4_BLOCKS
                         for (; r < r_end && !dead; ++r) group_row(r, std::integral_constant<int, 3>{}, WithBits{});
                         r_end = r;
@@ -1798,9 +1882,9 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
                     if (!(cls == 0 && r_beg == 0 && r_e == 16)) { DG_INC(dg_gen16, r_end - r_beg) DG_ADD2(dg_cyc_gen16) }
                     x = g0 + r_end;
 #ifdef PWR_DIAG
-                    if (lane == 0 && dg_log < 1270) {
+                    if (lane == 0 && dg_me && dg_log < 1270) {
                         unsigned long long *lg = jb.diag + ((size_t)job * 32 + wave) * 4096 + 256 + 3 * dg_log;
-                        lg[0] = (unsigned long long)x | ((unsigned long long)cls << 32) | ((unsigned long long)(r_end - r_beg) << 40); lg[1] = __builtin_amdgcn_s_memrealtime();
+                        lg[0] = (unsigned long long)x | ((unsigned long long)(cls | (warmup ? 16 : 0)) << 32) | ((unsigned long long)(r_end - r_beg) << 40); lg[1] = __builtin_amdgcn_s_memrealtime();
                         lg[2] = dg_wait_fast + dg_wait_gen + dg_wait_setup;
                     }
                     dg_log += 1;
@@ -1940,7 +2024,7 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
                 __builtin_amdgcn_s_sleep(1);
             }
 #ifdef PWR_DIAG
-            if (lane == 0 && dg_general < 36) {
+            if (lane == 0 && dg_me && dg_general < 36) {
                 unsigned long long *ev = jb.diag + ((size_t)job * 32 + wave) * 4096 + 16 + 3 * dg_general;
                 ev[0] = (unsigned long long)x; ev[1] = ev_t0; ev[2] = __builtin_amdgcn_s_memrealtime();
             }
@@ -2020,7 +2104,7 @@ __global__ __launch_bounds__(WG1 ? NW * 64 : 128) void k_fill_v3(DState st, JobB
     }
     V4_FLUSH()
 #ifdef PWR_DIAG
-    if (lane == 0) {
+    if (lane == 0 && dg_me) {
         unsigned long long *dgp = jb.diag + ((size_t)job * 32 + wave) * 4096;
         dgp[0] = __builtin_amdgcn_s_memtime() - t_clk0; dgp[1] = dg_wait_fast; dgp[2] = dg_wait_gen; dgp[3] = dg_wait_setup;
         dgp[4] = ((unsigned long long)dg_int << 32) | dg_gen16; dgp[5] = ((unsigned long long)dg_general << 32) | dg_nowork;

@@ -38,7 +38,7 @@ if os.environ.get("LOG"):
             print(f"  ---- wave {w}: per stretch: end row, role, rows, cycles/row busy, cycles/row waiting")
             pt, pw = None, None
             for (xc, t, wt) in full:
-                xx, cls_, nr = xc & 0xffffffff, (xc >> 32) & 0xff, xc >> 40
+                xx, cls_, nr = xc & 0xffffffff, (xc >> 32) & 0xf, xc >> 40      # (bit 36: a group of the warm-up, scripts/dev/role_pace.py)
                 if pt is not None and 1000 <= xx <= 1400:
                     dt = (t - pt) * 10 * 2.39
                     print(f"       x={xx:5d} role {cls_} rows {nr:2d}: busy {(dt-(wt-pw))/max(nr,1):6.0f}  wait {(wt-pw)/max(nr,1):6.0f}")

@@ -4,7 +4,8 @@ The straight-line groups of the fast path are 16 copies of one row; every row en
 row marker: `global_store_dwordx2 ... sc1`; the builds that published two words per row end it with
 `global_store_dwordx4 ... sc1`: set MARKER=global_store_dwordx4 in the environment for those).  The kernel's code is cut at these stores; a run of at least 12 pieces
 whose lengths differ by at most one (a wait state more or less) is one straight-line group, and its most frequent length is
-the row's instruction count.  The compiler lays the seven groups out in an order of its own, so they are named by size: the
+the row's instruction count; the s_nop among them are the wait states the compiler pads hazards with (a DPP operand two
+instructions behind its VALU write, ...), which cost a lone wave an issue slot like any instruction.  The compiler lays the seven groups out in an order of its own, so they are named by size: the
 three shortest are the warm-up's (no record) and the longest is the one with run-time flags; within the warm-up and within the
 own part INTERIOR < LEFT < RIGHT (a guard costs a compare and a select per cell, RIGHT posts the row minimum as well).
 Needs llvm-objdump of ROCm (no GPU)."""
@@ -61,9 +62,10 @@ def main():
         if j - i >= 12:
             n = max(set(gaps[i:j]), key=gaps[i:j].count)
             k = i + gaps[i:j].index(n)
-            kinds = {"v": 0, "s": 0, "ds": 0, "mem": 0}
+            kinds = {"v": 0, "s": 0, "ds": 0, "mem": 0, "nop": 0}
             for l in ins[marks[k] + 1:marks[k + 1] + 1]:
                 op = l.split()[0]
+                kinds["nop"] += op == "s_nop"                # (counted among the scalar ones too)
                 kinds["ds" if op.startswith("ds_") else "mem" if op.startswith(("global_", "buffer_", "flat_")) else "s" if op.startswith("s_") else "v"] += 1
             groups.append((n, kinds))
         i = max(j, i + 1)
@@ -75,7 +77,7 @@ def main():
             names[k] = name
     for k in sorted(range(len(groups)), key=lambda k: groups[k][0]):
         n, kinds = groups[k]
-        print("  %-20s %3d instructions per row (%d vector, %d scalar, %d LDS, %d store)" % (names.get(k, "group %d" % k), n, kinds["v"], kinds["s"], kinds["ds"], kinds["mem"]))
+        print("  %-20s %3d instructions per row (%d vector, %d scalar, %d LDS, %d store; %d of the scalar ones wait states)" % (names.get(k, "group %d" % k), n, kinds["v"], kinds["s"], kinds["ds"], kinds["mem"], kinds["nop"]))
 
 
 if __name__ == "__main__":
