@@ -48,6 +48,12 @@ PGR_EXPORTS = ["pgr_refine", "pgr_free", "pgr_last_timing", "pgr_read_window", "
                "pgr_last_assign_timing", "pgr_msa_settle", "pgr_settlement_free", "pgr_last_settle_timing", "pgr_tail_probe",
                "pgr_km_tail_probe"]
 
+# every symbol include/pfl.h declares (the flank labellings)
+PFL_EXPORTS = ["pfl_create", "pfl_destroy", "pfl_neighbours", "pfl_distances", "pfl_cluster", "pfl_get_stats", "pfl_labels",
+               "pfl_read_info", "pfl_free", "pfl_write_labels", "pfl_run_files"]
+PFL_MAX_REACH = 512
+PFL_MAX_FLANKS = 30000
+
 # constants of include/pgr.h that tests and scripts cite (pgr_cons_device.hip)
 PGR_MAX_ROWS = 30000
 PGR_CS_TILE = 1024            # window columns per work-group of k_cs_counts
@@ -361,5 +367,28 @@ def load():
     for n in ("pmc_tail_probe", "pgr_tail_probe", "pgr_km_tail_probe"):   # test hooks (tail_probe.py)
         getattr(lib, n).restype = ci
         getattr(lib, n).argtypes = [ci, pi, pd, ci, pd]
+    pub = ctypes.POINTER(ctypes.c_ubyte)
+    lib.pfl_create.restype = ci
+    lib.pfl_create.argtypes = [ctypes.POINTER(vp), ci]
+    lib.pfl_destroy.restype = None
+    lib.pfl_destroy.argtypes = [vp]
+    lib.pfl_neighbours.restype = ci
+    lib.pfl_neighbours.argtypes = [ci, pi, cp, pub, pi, pi, pi, pi, pi, pi]
+    lib.pfl_distances.restype = ci
+    lib.pfl_distances.argtypes = [vp, ci, cp, pll, pi, pi, ci, ci, pi, pi]
+    lib.pfl_cluster.restype = ci
+    lib.pfl_cluster.argtypes = [ci, pi, pi, ci, ci, pi]
+    lib.pfl_get_stats.restype = ci
+    lib.pfl_get_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), pd]
+    lib.pfl_labels.restype = ci
+    lib.pfl_labels.argtypes = [vp, ci, cp, pll, pi, cp, pub, ci, ci, ci, ci, pi, pi, pi]
+    lib.pfl_read_info.restype = ci
+    lib.pfl_read_info.argtypes = [cp, pi, ctypes.POINTER(vp)]
+    lib.pfl_free.restype = None
+    lib.pfl_free.argtypes = [vp]
+    lib.pfl_write_labels.restype = ci
+    lib.pfl_write_labels.argtypes = [cp, ci, pi]
+    lib.pfl_run_files.restype = ci
+    lib.pfl_run_files.argtypes = [cp, cp, cp, cp, ci, ci, ci, ci, cp, cp, ci, vp]
     _lib = lib
     return lib

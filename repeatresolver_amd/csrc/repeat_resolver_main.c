@@ -10,6 +10,10 @@
  *                     labels (pgr_connect): "<K_first> <K_last>", then K_first lines of K_last values in %f.  With -w a
  *                     missing MaxCorrsOf_ file is computed (pmc_maxcorrs at the -c coverage), written and read back, as
  *                     RR:3987-3999 intends.
+ *   -l <FlankingLeft> -r <FlankingRight>   (with -w, both or neither): two labellings of the MSA's rows, one integer per line
+ *                     (FlankClusterer writes them, include/pfl.h).  They go in front of and behind the windows' k-means labels
+ *                     into pgr_connect, as SDA:375 puts them, and ConnectionsOf_ is then the matrix from the left flanks'
+ *                     clusters to the right flanks'.  Without them nothing changes.
  * Undefined in the reference, defined here: a missing MaxCorrsOf_ file (the reference dereferences NULL, RR:3981; its own
  * AllMaxCorrsRechner behind RR:3987 is never reached) prints a message and exits 1, as does any other failure. */
 #include <stdio.h>
@@ -25,9 +29,23 @@ static int fail(const char *what, int rc)
     return 1;
 }
 
+/* a labelling of the MSA's rows from a file of one integer per line (pfl_write_labels) */
+static int read_labels(const char *path, int rows, int *out)
+{
+    FILE *f = fopen(path, "r");
+    int n = 0, v;
+    if (!f) return PWR_ERR_INPUT;
+    while (fscanf(f, "%d", &v) == 1) {
+        if (n == rows || v < -1) { fclose(f); return PWR_ERR_INPUT; }
+        out[n++] = v;
+    }
+    fclose(f);
+    return n == rows ? PWR_OK : PWR_ERR_INPUT;
+}
+
 /* -w: the windows of sites[nsites] in one call; returns the exit code */
 static int run_windows(const char *msa, int rows, int width, const unsigned char *text, const double *mc, int nsites, const int *sites,
-                       int cov, double cutoff, int device)
+                       int cov, double cutoff, int device, const char *flank_left, const char *flank_right)
 {
     pgr_msa *h = NULL;
     pgr_resolution rs;
@@ -50,11 +68,16 @@ static int run_windows(const char *msa, int rows, int width, const unsigned char
         printf("Parts: %d, %d, %d\n", w->dropoff_parts, w->reldrop_parts, w->kmeans_parts);
     }
     {
-        int *all = malloc(sizeof(int) * (size_t)rs.nwindows * (size_t)rows);
+        const int fl = flank_left ? 1 : 0;                                          /* a labelling in front and one behind */
+        int *all = malloc(sizeof(int) * (size_t)(rs.nwindows + 2 * fl) * (size_t)rows);
         if (!all) { fail("connections", PWR_ERR_NOMEM); goto done; }
-        for (int p = 0; p < rs.nwindows; p++) memcpy(all + (size_t)p * rows, rs.windows[p].kmeans_labels, sizeof(int) * (size_t)rows);
-        if (rs.nwindows < 2) { printf("One window: no connections.\n"); free(all); status = 0; goto done; }
-        rc = pgr_connect(rs.nwindows, rows, all, &cn);
+        for (int p = 0; p < rs.nwindows; p++) memcpy(all + (size_t)(p + fl) * rows, rs.windows[p].kmeans_labels, sizeof(int) * (size_t)rows);
+        if (fl) {
+            if ((rc = read_labels(flank_left, rows, all))) { fail(flank_left, rc); free(all); goto done; }
+            if ((rc = read_labels(flank_right, rows, all + (size_t)(rs.nwindows + 1) * rows))) { fail(flank_right, rc); free(all); goto done; }
+        }
+        if (rs.nwindows + 2 * fl < 2) { printf("One window: no connections.\n"); free(all); status = 0; goto done; }
+        rc = pgr_connect(rs.nwindows + 2 * fl, rows, all, &cn);
         free(all);
         if (rc) { fail("connections", rc); goto done; }
     }
@@ -84,6 +107,7 @@ int main(int argc, char **argv)
     int nsites = 0, windows = 0;
     int *sites = calloc((size_t)argc, sizeof(int));
     double cutoff = 0.0;
+    const char *flank_left = NULL, *flank_right = NULL;
     if (!sites) return fail("arguments", PWR_ERR_NOMEM);
     for (int i = 2; i < argc; i++) {
         if (argv[i][0] != '-') continue;
@@ -96,6 +120,8 @@ int main(int argc, char **argv)
         }
         if (argv[i][1] == 't' && i + 1 < argc) cutoff = atof(argv[i + 1]);                  /* RR:3942 */
         if (argv[i][1] == 'g' && i + 1 < argc) device = atoi(argv[i + 1]);
+        if (argv[i][1] == 'l' && i + 1 < argc) flank_left = argv[i + 1];
+        if (argv[i][1] == 'r' && i + 1 < argc) flank_right = argv[i + 1];
         if (argv[i][1] == 'w') {
             windows = 1; nsites = 0;
             for (int j = i + 1; j < argc && argv[j][0] != '-'; j++) {
@@ -111,6 +137,11 @@ int main(int argc, char **argv)
         }
     }
     if (windows && nsites < 2) { printf("RepeatResolver: -w needs at least two column numbers.\n"); free(sites); return 1; }
+    if ((flank_left || flank_right) && !(windows && flank_left && flank_right)) {
+        printf("RepeatResolver: -l and -r go together, and with -w.\n");
+        free(sites);
+        return 1;
+    }
     int rows = 0, width = 0, n = 0, rc, status = 1;
     unsigned char *text = NULL;
     double *mc = NULL;
@@ -140,7 +171,7 @@ int main(int argc, char **argv)
         return 1;
     }
     if (n != width * 5) { printf("RepeatResolver: %s holds %d values, the MSA has %d variations.\n", name, n, width * 5); goto done; }
-    if (windows) { status = run_windows(msa, rows, width, text, mc, nsites, sites, cov, cutoff, device); goto done; }
+    if (windows) { status = run_windows(msa, rows, width, text, mc, nsites, sites, cov, cutoff, device, flank_left, flank_right); goto done; }
     if ((rc = pgr_refine(rows, width, text, mc, von, bis, cov, cutoff, device, &res))) { fail("group refinement", rc); goto done; }
     printf("Cutoff %f\n", res.cutoff);                                                      /* RR:3984 */
     if ((rc = pgr_read_window(rows, width, text, von, bis, &win))) { fail("window", rc); goto done; }

@@ -61,12 +61,11 @@ def initial_msa(cfg: dg.SimConfig, device: int = 0, cutoff: float = 0.30, both_s
     return rows, info
 
 
-def initial_msa_from_reads(cfg: dg.SimConfig, device: int = 0, cutoff: float = 0.30, parts: int = 60, overlap: int = 0,
-                           error_cutoff: float = 0.30, both_strands: bool = False):
-    """The reference pipeline's own way in, from the *full* reads (no ground truth): writes the data set's reads FASTA
-    (datagen.write_dataset), runs the ReadCutter drop-in on it (GPU), then InitialAligner (GPU) on the Seq.fasta it wrote.
-    Returns (rows, info) like initial_msa.  both_strands: ReadCutter looks for its cut points in both orientations of every
-    read (`-b 1`) and InitialAligner takes each piece on the strand it aligns on; info["strands"] is the strand per piece."""
+def _front_from_reads(cfg, device, cutoff, parts, overlap, error_cutoff, both_strands):
+    """What initial_msa_from_reads and flank_labels both need: ReadCutter and InitialAligner on the full reads.  Returns
+    (rows, info, pieces, piece_read, classes): the pieces as Seq.fasta holds them (not turned), the read of each
+    (ReadSeqInfo) and its SeqClass letter."""
+    from .flanks import read_info
     from .initial_aligner import _clean
     from .read_cutter import run_files
     t0 = time.time()
@@ -86,6 +85,7 @@ def initial_msa_from_reads(cfg: dg.SimConfig, device: int = 0, cutoff: float = 0
             templ = _clean(b"".join(ln for ln in f.read().split(b"\n") if not ln.startswith(b">")))
         with open(seq_path, "rb") as f:
             reads = [_clean(r) for r in f.read().split(b">")[1:]]
+        pieces, piece_read = reads, read_info(rsi_path, len(reads))
         g = InitialAligner(templ, device=device)
         strands = None
         try:
@@ -114,7 +114,32 @@ def initial_msa_from_reads(cfg: dg.SimConfig, device: int = 0, cutoff: float = 0
     if strands is not None:
         info["strands"] = [int(v) for v in strands]
         info["reverse"] = int(sum(info["strands"]))
-    return rows, info
+    return rows, info, pieces, piece_read, classes
+
+
+def initial_msa_from_reads(cfg: dg.SimConfig, device: int = 0, cutoff: float = 0.30, parts: int = 60, overlap: int = 0,
+                           error_cutoff: float = 0.30, both_strands: bool = False):
+    """The reference pipeline's own way in, from the *full* reads (no ground truth): writes the data set's reads FASTA
+    (datagen.write_dataset), runs the ReadCutter drop-in on it (GPU), then InitialAligner (GPU) on the Seq.fasta it wrote.
+    Returns (rows, info) like initial_msa.  both_strands: ReadCutter looks for its cut points in both orientations of every
+    read (`-b 1`) and InitialAligner takes each piece on the strand it aligns on; info["strands"] is the strand per piece."""
+    return _front_from_reads(cfg, device, cutoff, parts, overlap, error_cutoff, both_strands)[:2]
+
+
+def flank_labels(cfg: dg.SimConfig, device: int = 0, cutoff: float = 0.30, parts: int = 60, overlap: int = 0,
+                 error_cutoff: float = 0.30, both_strands: bool = False, *, max_permille, reach: int = 256, min_len: int = 100,
+                 min_size: int = 1):
+    """initial_msa_from_reads, and what the connection of the windows lacks at both ends: the labelling of the rows by the
+    unique sequence left and right of them, from ReadCutter's own pieces (flanks.flank_labels on the GPU; no ground truth).
+    Returns (rows, info, left, right): left[t] / right[t] = the cluster of row t's flank on that side or -1, the shape
+    resolution.connect takes in front of and behind the windows' labellings.  info gains "pieces_list", "piece_read" and
+    "classes": the pieces as Seq.fasta holds them, the read of each and its SeqClass letter.  max_permille has no default."""
+    from .flanks import flank_labels as labels_of
+    rows, info, pieces, piece_read, classes = _front_from_reads(cfg, device, cutoff, parts, overlap, error_cutoff, both_strands)
+    left, right = labels_of(pieces, piece_read, classes, info.get("strands"), max_permille=max_permille, reach=reach,
+                            min_len=min_len, min_size=min_size, device=device)
+    info.update(pieces_list=pieces, piece_read=piece_read, classes=classes)
+    return rows, info, left, right
 
 
 def refined_groups(rows, von=None, bis=None, cov: int = 30, cutoff: float = 0.0, device: int = 0):
