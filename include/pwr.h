@@ -179,6 +179,11 @@ void pwr_snapshot_free(pwr_snapshot *snap);
  *   "ptrace"    traceback kernel: 2 = k_trace_blk (default: one wave per 64 rows, no hand-over chain), 1 = k_trace_par (64 chunks
  *               handing over top-down), 0 = k_trace_wp (one wave per job)
  *   "slack"     spare column capacity kept when the device arrays are (re)allocated
+ *   "grows", "grows_mid_batch"
+ *               read-only, counted on the host since the context was made: the times the column arrays were regrown because a
+ *               commit found them too small, and those of them where earlier jobs of the same batch had committed before the
+ *               job that did not fit (the row pointer has moved on then, and the batch's plan is dropped: the batch after the
+ *               regrow takes the next rows in order)
  *   "spec_len"  percent a speculative row may be longer than the first row of its batch (default 6)
  * "fill", "waves", "slack", "src_start" and the "seg" options must be set before the first call that touches the device. */
 int pwr_set_option(pwr_ctx *ctx, const char *key, long value);

@@ -3905,6 +3905,12 @@ __global__ __launch_bounds__(COMMIT_NT) void k_commit_finish(DState st, JobBufs 
                 s_pl[7] = hh->evrate * 100.0f < fminf((float)jb.plan_evrate_x100, jb.plan_gate_rel ? (float)jb.plan_slack * (100.0f / 128.0f) : 3.0e38f) ? 1 : 0;
                 s_jm = hh->jumpmask; s_ev = (unsigned)hh->events_total;
                 if (!s_pl[0]) st.bplan[0] = 0;                                     // the next rows in order
+            } else if (hh->status != 0 || hh->need_grow) {
+                // No plan is made for the next batch, and the one this batch ran by must not outlive it: the jobs before the one
+                // that stopped the batch have committed, next_row, ahead and jumpmask have moved on by `adv`, and the plan's offsets
+                // and gaps count from the row pointer as it stood.  After the regrow the next batch takes the next rows in order.
+                // (The jump records behind JR_BASE stay: they belong to rows, not to the plan.)
+                st.bplan[0] = 0;
             }
         }
     }
@@ -4136,6 +4142,7 @@ struct pwr_ctx {
     int spec_len = 6;                     // percent a speculative row may be longer than the first row of its batch (option "spec_len")
     int fill_mode = 4;                    // 4: k_fill_v3 (one work-group per wave, default), 3: k_fill_v2 (one work-group per DP; cross-check and fallback)
     double host_enqueue_s = 0, host_wait_s = 0;   // diagnostic: time the host spent enqueueing batches / waiting for their headers (read-only options)
+    long grows = 0, grows_mid_batch = 0;          // regrows of the column arrays; those of them after earlier jobs of the same batch had committed (read-only options)
     unsigned host_seq = 0;                // sequence number of the header copies the commit kernels leave in pinned memory
     int seen_fallback = 0, seen_need64 = 0;   // Hdr::fallback / need64 as the host last saw them: the batches it enqueues bring k_fill_v2 / k_fill64 along
     int trace_epoch = 0;                  // k_trace_par launch counter (22 bits)
@@ -4728,13 +4735,19 @@ static int regrow(pwr_ctx *c, T **p, size_t keep, size_t ncap)
 }
 
 // A commit found the column arrays too small (Hdr::need_grow): make room for at least `growth` more columns.  The stream
-// is idle when this runs.
-static int grow_state(pwr_ctx *c, long long growth)
+// is idle when this runs.  `ncommitted`: the jobs of the batch that was stopped which committed before the one that did not
+// fit -- the row pointer has moved on with them then, and the plan that batch ran by (DState::bplan, offsets from the row
+// pointer as it stood) says nothing about the rows that follow: the next batch takes them in order.  (k_commit_finish
+// has dropped the plan already; here once more, for every path that goes on after a regrow.)
+static int grow_state(pwr_ctx *c, long long growth, int ncommitted)
 {
     Hdr h;
     int rc = read_hdr(c, &h);
     if (rc) return rc;
     if (h.status) return h.status;
+    c->grows += 1;
+    if (ncommitted > 0) c->grows_mid_batch += 1;
+    HIPC(hipMemsetAsync(c->st.bplan, 0, sizeof(int), c->stream));                 // (the jump records and Hdr::jumpmask stay: they belong to rows)
     DState &st = c->st;
     const size_t ncap = ((size_t)std::max<long long>(2LL * st.colcap, (long long)std::max(h.W, h.nslots) + 2 * growth + 8192) + 15) & ~(size_t)15;
     const size_t ocol = st.colcap, oslot = st.slotcap;
@@ -5016,7 +5029,7 @@ static int realign_positions(pwr_ctx *c, int k0, int n, bool resume = false)   /
             HIPC(hipStreamSynchronize(c->stream));
             long long growth = 0;
             for (int j = 0; j < c->window && h.next_row + j < kend; ++j) growth += c->rowlen[c->ids[h.next_row + j]];
-            if ((rc = grow_state(c, growth))) return rc;
+            if ((rc = grow_state(c, growth, h.ncommitted))) return rc;
             return realign_positions(c, h.next_row, kend - h.next_row, true);
         }
         if (h.next_row >= kend) break;
@@ -5127,7 +5140,7 @@ static int split_commit(pwr_ctx *c, const void *recv_dev, int *rows_left)
         // every replica finds the same shortage in the same batch and regrows alike; the slab goes on where it stands
         long long growth = 0;
         for (int j = 0; j < c->window && h.next_row + j < c->split_kend; ++j) growth += c->rowlen[c->ids[h.next_row + j]];
-        if ((rc = grow_state(c, growth))) return rc;
+        if ((rc = grow_state(c, growth, h.ncommitted))) return rc;
     }
     *rows_left = std::max(0, h.row_end - h.next_row);
     return PWR_OK;
@@ -5313,6 +5326,8 @@ extern "C" int pwr_get_option(pwr_ctx *c, const char *key, long *value)
         *value = 0;
         if (c->on_device) { Hdr h; int rc = read_hdr(c, &h); if (rc) return rc; *value = (long)(h.evrate * 100.0f); }
     }
+    else if (!strcmp(key, "grows")) *value = c->grows;                        // since the context was made
+    else if (!strcmp(key, "grows_mid_batch")) *value = c->grows_mid_batch;
     else if (!strcmp(key, "host_enqueue_us")) *value = (long)(c->host_enqueue_s * 1e6);   // since the context was made
     else if (!strcmp(key, "host_wait_us")) *value = (long)(c->host_wait_s * 1e6);
     else if (!strcmp(key, "warm_now")) {                                      // percent of the bandwidth a warm-up covers right now

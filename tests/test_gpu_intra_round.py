@@ -28,6 +28,10 @@ def _workload(name):
         cfg = dg.SimConfig(kind="Tree", copies=6, coverage=12, difference=0.01, repeat_len=6000, flank=1500,
                            length_scale=0.03, min_aligned=60, seed=31)
         return [bytes(r) for r in dg.build_msa(dg.simulate(cfg))], 100, {"window": 16, "slack": 0}
+    if name == "plan_regrow":                              # designed: the regrow comes in mid-batch, at a row picked ahead (plan_cases.py)
+        import plan_cases as pc
+        rows, bw, _ = pc.regrow_case(pc.SEEDS[0])
+        return rows, bw, {"window": 3, "slack": 0}
     return split_rows(golden_input(name)), 1000, {"window": 4}
 
 
@@ -42,9 +46,11 @@ def _oracle_rounds(oracle, rows, bw, rounds):
     return out
 
 
-@pytest.mark.parametrize("name", ["toy_b_b1000", "churn"])
+@pytest.mark.parametrize("name", ["toy_b_b1000", "churn", "plan_regrow"])
 def test_split_round_with_one_replica(name, oracle):
-    """world = 1: the staged form of a batch (front half, export, import of nothing, commit) run by the per-batch loop."""
+    """world = 1: the staged form of a batch (front half, export, import of nothing, commit) run by the per-batch loop.
+    "plan_regrow" regrows in pwr_split_commit after earlier jobs of the batch have committed, while the batch's plan holds a
+    row picked ahead."""
     from repeatresolver_amd.intra_round import SplitRound
     from repeatresolver_amd.realigner import PWReAligner
     rows, bw, opts = _workload(name)
@@ -56,6 +62,8 @@ def test_split_round_with_one_replica(name, oracle):
         sr.realign_round()
         assert g.total_score() == exp[rnd][0]
         assert g.export_rows() == exp[rnd][1]
+        if name == "plan_regrow" and rnd == 0:
+            assert g.get_option("grows_mid_batch") >= 1 and g.stats()["rows_jumped"] >= 1
     assert g.stats()["cells_reference"] == exp[1][2]
     # ... and the context goes on as an ordinary one afterwards (every job its own again)
     g.realign_round()
@@ -110,10 +118,11 @@ def _run_ranks(world, backend, name, rounds):
     return got
 
 
-@pytest.mark.parametrize("name", ["toy_b_b1000", "churn"])
+@pytest.mark.parametrize("name", ["toy_b_b1000", "churn", "plan_regrow"])
 def test_split_round_over_two_ranks(name, oracle):
     """Two replicas (gloo, one GPU): each fills and traces every other job of every batch; after every round both hold the
-    reference's MSA.  "churn" regrows the column arrays in mid-slab (slack 0) and commits rows ahead of stale ones."""
+    reference's MSA.  "churn" regrows the column arrays in mid-slab (slack 0) and commits rows ahead of stale ones;
+    "plan_regrow" regrows them in mid-batch, at a row the batch before picked ahead."""
     rows, bw, _ = _workload(name)
     rounds = 2
     exp = _oracle_rounds(oracle, rows, bw, rounds)
