@@ -306,7 +306,7 @@ int pgr_resolvability(int parts, const int *diff, int *unique11, int *min_diff, 
  * best and second are part INDICES 0 .. parts - 1, not labels.  Everything is an integer, computed without atomics: no result
  * depends on an order. */
 #define PGR_AS_SCRATCH_BYTES (64 << 20)   /* most device scratch per range of rows (planes + mismatch matrix) */
-#define PGR_AS_TILE 8            /* parts per work-group of the distance kernel (pgr_assign_device.hip) */
+#define PGR_AS_TILE 8            /* parts per work-group of the distance kernels (row_planes.h: k_as_dist, k_st_dist) */
 
 typedef struct {
     int rows, parts, ncolumns;

@@ -53,6 +53,17 @@ struct DevArena {
     }
     ~DevArena() { for (void *p : all) (void)hipFree(p); }
 };
+
+// n halved (rounding up) while fits(n) says that the device refuses the buffers of that size; the refusal's HIP error, which
+// would stick, is cleared.  PWR_ERR_NOMEM when not even n == 1 fits.  fits() lets go of what a refused attempt has got.
+template <class F> int largest_that_fits(int &n, F fits)
+{
+    for (; !fits(n); n = (n + 1) / 2) {
+        (void)hipGetLastError();
+        if (n == 1) return PWR_ERR_NOMEM;
+    }
+    return PWR_OK;
+}
 }   // namespace
 
 #endif /* PWR_DEV_UTIL_H */

@@ -169,15 +169,8 @@ static int consensus(const pgr_msa *h, const int *labels, int von, int bis, cons
 {
     const int rows = h->rows, width = h->width;
     const double t0 = now_ms();
-    if (von == -1 && bis == -1) { von = 0; bis = width - 1; }
-    if (von < 0 || bis >= width || von > bis) return PWR_ERR_ARG;
-    int top = -1;
-    for (int r = 0; r < rows; ++r) {
-        if (labels[r] < -1) return PWR_ERR_ARG;
-        if (labels[r] > top) top = labels[r];
-    }
-    if (top >= PGR_MAX_ROWS) return PWR_ERR_RANGE;
-    if (top < 0) return PWR_ERR_ARG;
+    const int top = pgr_window_and_top(labels, rows, width, &von, &bis);
+    if (top < 0) return top;
     const int W = bis + 1 - von;
 
     // GroupMaker (TA:159-160): the labels that occur, ascending; the rows counting-sorted by part
@@ -196,17 +189,7 @@ static int consensus(const pgr_msa *h, const int *labels, int von, int bis, cons
         }
     const int nchunks = (int)(chunk.size() / 4);
 
-    // SignaturesMaker's columns (TA:263, TA:157), in doubles on the host
-    std::vector<int> selected;
-    for (int x = von; x <= bis; ++x) {
-        bool in = true;
-        if (maxcorrs_full) {
-            double m = maxcorrs_full[(size_t)x * 5];
-            for (int i = 1; i < 5; ++i) if (maxcorrs_full[(size_t)x * 5 + i] > m) m = maxcorrs_full[(size_t)x * 5 + i];
-            in = m > cutoff;
-        }
-        if (in) selected.push_back(x);
-    }
+    const std::vector<int> selected = pgr_signature_columns(von, bis, maxcorrs_full, cutoff);
 
     const size_t PW = (size_t)P * W, PP = (size_t)P * P;
     o->rows = rows; o->von = von; o->bis = bis; o->width = W; o->parts = P; o->nselected = (int)selected.size();
@@ -234,13 +217,7 @@ static int consensus(const pgr_msa *h, const int *labels, int von, int bis, cons
     long long per = (long long)PGR_CS_SCRATCH_INTS / ((long long)P * 5 * PGR_CS_TILE);
     int rt = (int)std::max(1LL, std::min((long long)tiles, per));
     std::optional<Range> rg;
-    for (;; rt = (rt + 1) / 2) {
-        rg.emplace();
-        if (rg->get((size_t)P, (size_t)rt * PGR_CS_TILE)) break;
-        (void)hipGetLastError();
-        rg.reset();
-        if (rt == 1) return PWR_ERR_NOMEM;
-    }
+    if (const int rc = largest_that_fits(rt, [&](int n) { return rg.emplace().get((size_t)P, (size_t)n * PGR_CS_TILE); })) return rc;
     const int cw = rt * PGR_CS_TILE;
     HIPC(hipDeviceSynchronize());
     double t = now_ms(), u;

@@ -33,4 +33,41 @@ extern "C"
 #endif
 __attribute__((visibility("hidden"))) void pgr_word_major(const unsigned long long *sets, int sc, const int *pick, size_t n,
                                                           unsigned long long *out);
+
+#ifdef __cplusplus
+#include <vector>
+
+/* What pgr_msa_consensus and pgr_msa_settle do with a labelling and a window before anything else: von == bis == -1 is the
+ * whole width.  The largest label, or PWR_ERR_ARG for a window outside the text, a label below -1 or no label at all, or
+ * PWR_ERR_RANGE for a label from PGR_MAX_ROWS on. */
+static inline int pgr_window_and_top(const int *labels, int rows, int width, int *von, int *bis)
+{
+    if (*von == -1 && *bis == -1) { *von = 0; *bis = width - 1; }
+    if (*von < 0 || *bis >= width || *von > *bis) return PWR_ERR_ARG;
+    int top = -1;
+    for (int r = 0; r < rows; ++r) {
+        if (labels[r] < -1) return PWR_ERR_ARG;
+        if (labels[r] > top) top = labels[r];
+    }
+    if (top >= PGR_MAX_ROWS) return PWR_ERR_RANGE;
+    return top < 0 ? PWR_ERR_ARG : top;
+}
+
+/* SignaturesMaker's columns of [von, bis] (TA:263, TA:157), in doubles on the host: those whose largest of the five MaxCorrs
+ * exceeds the cutoff; every column where maxcorrs_full is null */
+static inline std::vector<int> pgr_signature_columns(int von, int bis, const double *maxcorrs_full, double cutoff)
+{
+    std::vector<int> columns;
+    for (int x = von; x <= bis; ++x) {
+        bool in = true;
+        if (maxcorrs_full) {
+            double m = maxcorrs_full[(size_t)x * 5];
+            for (int i = 1; i < 5; ++i) if (maxcorrs_full[(size_t)x * 5 + i] > m) m = maxcorrs_full[(size_t)x * 5 + i];
+            in = m > cutoff;
+        }
+        if (in) columns.push_back(x);
+    }
+    return columns;
+}
+#endif
 #endif

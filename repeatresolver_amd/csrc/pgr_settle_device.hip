@@ -6,9 +6,9 @@
 // existing entries, which the header writes out, and everything is an integer.  The rows' bit planes over the candidate columns
 // do not change between iterations, only the labels do: the planes are made once (k_st_planes) and stay resident; an iteration
 // reads no text, does no host arithmetic and sends one record of four ints to the host.
-//   k_st_planes   once per call: k_as_planes of pgr_assign_device.hip over all rows, stored as planes[word][row][valid, bit0,
-//                 bit1, bit2]: the four words of a (word, row) are 32 neighbouring bytes, because k_st_cons gathers rows -- in
-//                 k_as_planes' layout [word][plane][row] each of the four would cost it a 64-byte line of its own.
+//   k_st_planes   once per call: the plane body of row_planes.h (k_as_planes of pgr_assign_device.hip) over all rows:
+//                 planes[word][row] = {valid, bit0, bit1, bit2}.  The four words of a (word, row) are 32 neighbouring bytes, and
+//                 k_st_cons gathers rows: were they apart, each of the four would cost it a 64-byte line of its own.
 //   k_st_hist     per iteration: the rows of every label (integer atomics onto zeros).
 //   k_st_scan     one work-group: the labels that occur, ascending, are the parts of this iteration: part_of[label],
 //                 part_label[part], the offsets of the parts in order[]; it zeroes the histogram again and starts the record.
@@ -21,16 +21,15 @@
 //                 ballot of depth >= min_depth its column-ok word.
 //   k_st_mask     a wave per word: the AND of the living parts' ok words and of the candidate tail; its population count is
 //                 added to the record's ncolumns.
-//   k_st_dist     k_as_dist with valid & mask[word], the number of parts from the record.
-//   k_st_label    a thread per row: best and second over the living parts (k_as_best), the label rule, hold, the new label;
-//                 the changed rows by a block count and one integer atomic add.
+//   k_st_dist     the distance body of row_planes.h (k_as_dist) with valid & mask[word], the number of parts from the record.
+//   k_st_label    a thread per row: best and second over the living parts (row_planes.h, as k_as_best), the label rule, hold,
+//                 the new label; the changed rows by a block count and one integer atomic add.
 // A part that has died takes no work: the grids are sized for the parts of the initial labelling (parts are never born)
 // and a work-group behind the living parts returns at once.  The per-row results, part_label and mask are kept for two
 // iterations (index: iteration & 1), because an iteration that finds no column must leave the one before intact.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -40,45 +39,21 @@
 #include "dev_util.h"
 #include "pgr.h"
 #include "pgr_internal.h"
+#include "row_planes.h"
 
-#define ST_TP PGR_AS_TILE        // parts per tile of k_st_dist
-#define ST_NW 16                 // waves of a work-group of k_st_dist: they share the words
-#define ST_ROWS 64               // rows per work-group of k_st_dist: one per lane
 #define ST_CW 4                  // waves of a work-group of k_st_cons: they share the part's rows
 #define ST_SCAN 1024             // threads of k_st_scan
-static_assert(ST_TP == 8, "3 x 8 plane words of a tile are 48 scalar registers; eight counters per thread");
-
-typedef unsigned long long u64;
 
 // the record of an iteration, the only thing the host reads inside the loop
 enum { REC_CHANGED = 0, REC_PARTS = 1, REC_NCOLUMNS = 2, REC_ANY = 3, REC_INTS = 4 };
 
 static double g_st_ms[5] = {0, 0, 0, 0, 0};
 
-// grid (words, groups of 4 x 64 rows), 256 threads: k_as_planes of pgr_assign_device.hip over all R rows; planes[word][row]
+// grid (words, groups of 4 x 64 rows), 256 threads: all R rows of the text; planes[word][row]
 __global__ __launch_bounds__(256) void k_st_planes(long long width, int R, int ncolumns, const unsigned char *__restrict__ text,
                                                    const int *__restrict__ columns, ulonglong4 *__restrict__ planes)
 {
-    const int lane = threadIdx.x & 63, row0 = (blockIdx.y * 4 + (int)(threadIdx.x >> 6)) * 64;
-    if (row0 >= R) return;                                             // (the same for the whole wave)
-    const int w = blockIdx.x, j = w * 64 + lane, n = min(64, R - row0);
-    const bool in = j < ncolumns;                                      // a lane behind the last column loads nothing and is valid nowhere
-    const unsigned char *p = text + (long long)row0 * width + (in ? columns[j] : 0);
-    u64 keep[4] = {0, 0, 0, 0};
-    for (int i0 = 0; i0 < n; i0 += 8) {
-        unsigned int ch[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i)                                    // eight loads in flight; behind the group's last row that row again, kept by no lane
-            ch[i] = in ? p[(long long)min(i0 + i, n - 1) * width] : ' ';
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const unsigned int f = ch[i] | 0x20u;                      // base_code.h as one compare per symbol: the result is the ballot
-            const u64 c = __ballot(f == 'c'), g = __ballot(f == 'g'), t = __ballot(f == 't');
-            const u64 gap = __ballot(ch[i] == '-') | __ballot(ch[i] == '_'), v = __ballot(f == 'a') | c | g | t | gap;
-            if (lane == i0 + i) { keep[0] = v; keep[1] = c | t; keep[2] = g | t; keep[3] = gap; }
-        }
-    }
-    if (lane < n) planes[(size_t)w * R + row0 + lane] = make_ulonglong4(keep[0], keep[1], keep[2], keep[3]);   // 2 KB per wave, contiguous
+    row_planes_group(width, 0, R, ncolumns, text, columns, planes);
 }
 
 // a thread per row: size[label] += 1 (onto the zeros k_st_scan leaves)
@@ -208,43 +183,16 @@ __global__ __launch_bounds__(256) void k_st_mask(int nw, int ncandidates, int pp
     }
 }
 
-// grid (R / ST_ROWS, tiles of the initial parts), 64 * ST_NW threads: k_as_dist of pgr_assign_device.hip, the row's valid word
-// under mask[word]; mat[row][ppad]
-__global__ __launch_bounds__(64 * ST_NW) void k_st_dist(int R, int ppad, int nw, const int *__restrict__ rec,
+// grid (R / RP_ROWS, tiles of the initial parts), 64 * RP_NW threads: the row's valid word under mask[word]; mat[row][ppad]
+__global__ __launch_bounds__(64 * RP_NW) void k_st_dist(int R, int ppad, int nw, const int *__restrict__ rec,
                                                         const ulonglong4 *__restrict__ planes, const u64 *__restrict__ pp,
                                                         const u64 *__restrict__ mask, int *__restrict__ mat,
                                                         int *__restrict__ compared)
 {
-    __shared__ int red[ST_NW][ST_TP + 1][64];                          // every wave's counters, the last one compared
-    const int lane = threadIdx.x & 63, p0 = blockIdx.y * ST_TP, row = blockIdx.x * ST_ROWS + lane;
     const int parts = rec[REC_PARTS];
-    if (p0 >= parts || rec[REC_NCOLUMNS] == 0) return;                 // (the same for the whole work-group)
-    const int slice = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const bool has = row < R;
-    int m[ST_TP], cmp = 0;
-#pragma unroll
-    for (int a = 0; a < ST_TP; ++a) m[a] = 0;
-    for (int w = slice; w < nw; w += ST_NW) {
-        // the row's four words are 32 neighbouring bytes, a wave's 2 KB; a thread without a row loads nothing and is valid nowhere
-        const ulonglong4 r = has ? planes[(size_t)w * R + row] : make_ulonglong4(0, 0, 0, 0);
-        const u64 rv = r.x & mask[w], r0 = r.y, r1 = r.z, r2 = r.w;
-        const u64 *q = pp + (size_t)w * 3 * ppad + p0;                 // (the same address in every lane: scalar loads)
-        cmp += __popcll(rv);
-#pragma unroll
-        for (int a = 0; a < ST_TP; ++a) m[a] += __popcll(((r0 ^ q[a]) | (r1 ^ q[ppad + a]) | (r2 ^ q[2 * (size_t)ppad + a])) & rv);
-    }
-#pragma unroll
-    for (int a = 0; a < ST_TP; ++a) red[slice][a][lane] = m[a];
-    red[slice][ST_TP][lane] = cmp;
-    __syncthreads();
-    for (int j = slice; j <= ST_TP; j += ST_NW) {                      // counter j of all waves, by wave j
-        int sum = 0;
-#pragma unroll
-        for (int o = 0; o < ST_NW; ++o) sum += red[o][j][lane];
-        if (!has) continue;
-        if (j == ST_TP) { if (blockIdx.y == 0) compared[row] = sum; }
-        else if (p0 + j < parts) mat[(size_t)row * ppad + p0 + j] = sum;
-    }
+    if ((int)blockIdx.y * RP_TP >= parts || rec[REC_NCOLUMNS] == 0) return;   // a tile of dead parts, or no column (the same for the whole work-group)
+    __builtin_assume(mask != nullptr);                                 // (so that the body's test of it goes, as with k_as_dist's literal)
+    row_part_distances(R, parts, ppad, ppad, nw, planes, pp, mask, mat, compared);
 }
 
 // a thread per row; per_row = compared, best, second and the two counts of this iteration, R each.  init = the initial labels
@@ -258,18 +206,8 @@ __global__ __launch_bounds__(256) void k_st_label(int R, int ppad, int min_compa
     int moved = 0, any = 0;
     if (r < R) {
         const int cmp = per_row[r];
-        int b = -1, s = -1, bm = INT_MAX, sm = INT_MAX;
-        if (cmp > 0) {
-            const int *row = mat + (size_t)r * ppad;
-            for (int p = 0; p < parts; ++p) {
-                const int v = row[p];
-                // the best that is displaced becomes the second: it is smaller than the second, or equal and of lower index
-                if (v < bm) { s = b; sm = bm; b = p; bm = v; }
-                else if (v < sm) { s = p; sm = v; }
-            }
-        }
-        if (b < 0) bm = 0;
-        if (s < 0) sm = 0;
+        const BestSecond x = best_and_second(mat + (size_t)r * ppad, parts, cmp);
+        const int b = x.b, s = x.s, bm = b < 0 ? 0 : x.bm, sm = s < 0 ? 0 : x.sm;
         per_row[(size_t)R + r] = b; per_row[2 * (size_t)R + r] = s; per_row[3 * (size_t)R + r] = bm; per_row[4 * (size_t)R + r] = sm;
         int l = b >= 0 && cmp >= min_compared && (s == -1 || sm - bm >= min_margin) ? part_label[b] : -1;
         if (init && init[r] >= 0) l = init[r];
@@ -312,32 +250,16 @@ static int settle(const pgr_msa *h, const int *labels, int von, int bis, const d
     const double t0 = now_ms();
     const int rows = h->rows, width = h->width;
     if (max_iter < 1 || min_depth < 1 || min_compared < 0 || min_margin < 0) return PWR_ERR_ARG;
-    if (von == -1 && bis == -1) { von = 0; bis = width - 1; }          // from here on as pgr_msa_consensus
-    if (von < 0 || bis >= width || von > bis) return PWR_ERR_ARG;
-    int top = -1;
-    for (int r = 0; r < rows; ++r) {
-        if (labels[r] < -1) return PWR_ERR_ARG;
-        if (labels[r] > top) top = labels[r];
-    }
-    if (top >= PGR_MAX_ROWS) return PWR_ERR_RANGE;
-    if (top < 0) return PWR_ERR_ARG;
+    const int top = pgr_window_and_top(labels, rows, width, &von, &bis);   // as pgr_msa_consensus
+    if (top < 0) return top;
     const int L = top + 1;                                             // no label above `top` ever appears: a row takes a part's label or keeps its own
     std::vector<char> seen((size_t)L, 0);
     int P0 = 0;                                                        // the parts of the initial labelling: parts die, none is born
     for (int r = 0; r < rows; ++r)
         if (labels[r] >= 0 && !seen[labels[r]]) { seen[labels[r]] = 1; ++P0; }
 
-    // the candidate columns, fixed for the call: SignaturesMaker's (TA:263, TA:157) in doubles on the host, or the whole window
-    std::vector<int> cand;
-    for (int x = von; x <= bis; ++x) {
-        bool in = true;
-        if (maxcorrs_full && !all_columns) {
-            double m = maxcorrs_full[(size_t)x * 5];
-            for (int i = 1; i < 5; ++i) if (maxcorrs_full[(size_t)x * 5 + i] > m) m = maxcorrs_full[(size_t)x * 5 + i];
-            in = m > cutoff;
-        }
-        if (in) cand.push_back(x);
-    }
+    // the candidate columns, fixed for the call: SignaturesMaker's, or the whole window
+    const std::vector<int> cand = pgr_signature_columns(von, bis, all_columns ? nullptr : maxcorrs_full, cutoff);
     const int nc = (int)cand.size();
 
     o->rows = rows;
@@ -350,7 +272,7 @@ static int settle(const pgr_msa *h, const int *labels, int von, int bis, const d
 
     if (hipSetDevice(h->device) != hipSuccess) return PWR_ERR_DEVICE;
     const size_t R = (size_t)rows;
-    const int nw = (nc + 63) / 64, ppad = (P0 + ST_TP - 1) / ST_TP * ST_TP;
+    const int nw = (nc + 63) / 64, ppad = (P0 + RP_TP - 1) / RP_TP * RP_TP;
     DevArena mem;
     int *d_cand = mem.put(cand.data(), cand.size());
     int *d_lab[2] = {mem.put(labels, R), mem.get<int>(R)};
@@ -390,7 +312,7 @@ static int settle(const pgr_msa *h, const int *labels, int von, int bis, const d
         hipLaunchKernelGGL(k_st_cons, dim3(nw, P0), dim3(64 * ST_CW), 0, 0, rows, ppad, min_depth, (const int *)d_rec, (const ulonglong4 *)d_planes,
                            (const int *)d_order, (const int *)d_offset, d_pp, d_ok);
         hipLaunchKernelGGL(k_st_mask, dim3((nw + 3) / 4), dim3(256), 0, 0, nw, nc, ppad, (const u64 *)d_ok, mask, d_rec);
-        hipLaunchKernelGGL(k_st_dist, dim3((rows + ST_ROWS - 1) / ST_ROWS, ppad / ST_TP), dim3(64 * ST_NW), 0, 0, rows, ppad, nw,
+        hipLaunchKernelGGL(k_st_dist, dim3((rows + RP_ROWS - 1) / RP_ROWS, ppad / RP_TP), dim3(64 * RP_NW), 0, 0, rows, ppad, nw,
                            (const int *)d_rec, (const ulonglong4 *)d_planes, (const u64 *)d_pp, (const u64 *)mask, d_mat, per_row);
         hipLaunchKernelGGL(k_st_label, dim3(rb), dim3(256), 0, 0, rows, ppad, min_compared, min_margin, (const int *)d_mat,
                            (const int *)part_label, (const int *)d_init, (const int *)d_lab[cur], d_lab[cur ^ 1], per_row, d_rec);

@@ -10,7 +10,7 @@ import as_checker as ac
 import cs_cases as cs
 import ta_checker as ta
 
-KERNEL_TILE = 8                                                       # PGR_AS_TILE of include/pgr.h: parts per work-group of k_as_dist
+KERNEL_TILE = 8                                                       # PGR_AS_TILE of include/pgr.h: parts per work-group of k_as_dist and k_st_dist (row_planes.h)
 KERNEL_SCRATCH_BYTES = 64 << 20                                       # PGR_AS_SCRATCH_BYTES: planes and matrix of one range of rows
 FIELDS = ("compared", "best", "second", "best_mismatches", "second_mismatches")
 
