@@ -3,7 +3,8 @@ labellings that come out of them, the drop-in and RepeatResolver's -l / -r.
 
 The kernel is compiled per number of 32-row pattern words (1 .. 16), a wave takes one pattern and 64 texts, and a text has
 between m and m + m / 4 bases: the lengths below straddle the word boundaries, the reach, the end of the text's slack and the
-64-text tile; flanks of equal a are ordered by their index."""
+64-text tile; flanks of equal a are ordered by their index.  test_gpu_kernel_widths.py runs every one of the 16 word counts,
+each at the first and the last pattern length of its word."""
 import numpy as np
 import pytest
 

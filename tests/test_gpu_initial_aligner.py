@@ -104,7 +104,8 @@ def test_default_output_names_follow_the_template_path(tmp_path):
 @pytest.mark.parametrize("L2", [1, 2, 31, 32, 33, 64, 2047, 2048, 2049, 4100])
 def test_lane_and_word_boundaries(L2, ia_oracle):
     """template lengths around the 32-column words and the 64 x 32 columns one lane step covers; reads of 0, 1, 63, 64,
-    65 ... bases (the 64 rows in flight per wave), small alphabets (many ties), unrelated reads (wide bands)"""
+    65 ... bases (the 64 rows in flight per wave), small alphabets (many ties), unrelated reads (wide bands).  These
+    lengths reach 1, 2 and 3 words per lane; test_gpu_kernel_widths.py runs every width up to 35."""
     import random
     rng = random.Random(1000 + L2)
     reads = []

@@ -39,6 +39,8 @@ def _mutate(rng, s, rate):
 @pytest.mark.gpu
 @pytest.mark.parametrize("ln", [1, 31, 32, 33, 64, 500, 512, 513, 2049, 40000])
 def test_occurrences_equal_checker(ln):
+    """random jobs around the 32-row word and the 64 lanes of a wave; these lengths reach 1, 2 and 20 words per lane and
+    G = 1, 2, 16, 32, 64: test_gpu_kernel_widths.py runs every width and every G"""
     rng = random.Random(ln)
     rs = lambda n: "".join(rng.choice("acgt") for _ in range(n))
     big = ln >= 2049

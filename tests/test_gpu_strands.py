@@ -46,7 +46,8 @@ def _check(templ, reads, oracle, mem_budget=None, expected=None):
 
 @pytest.mark.parametrize("L2", [1, 31, 32, 33, 2047, 2048, 2049, 4100])
 def test_lane_and_word_boundaries_on_both_strands(L2, oracle):
-    """the read set of test_lane_and_word_boundaries with its three alphabets, every read also as its reverse complement"""
+    """the read set of test_lane_and_word_boundaries with its three alphabets, every read also as its reverse complement
+    (1, 2 and 3 words per lane; test_gpu_kernel_widths.py runs every width up to 35 on both strands)"""
     rng = random.Random(1000 + L2)
     nreads = 0
     for alpha in (b"a", b"ac", b"acgt"):
