@@ -161,8 +161,6 @@ struct CommitJob {                  // what k_commit_scan found out about a job 
     int u0, u1;                     // the columns the row covers before or after: every change lies in [u0, u1], every event in [u0 - 1, u1]
     int scanned, pad;
 };
-struct BatchPlan;
-struct CommitEv;
 struct JobBufs {
     GatherPart *gpart;             // [njobs][GATHER_G] partial results of the gather's shares
     unsigned gather_tag;           // launch counter of the gather (tags the partial results)
@@ -217,15 +215,12 @@ struct JobBufs {
     // job of a batch, but fills and traces only the jobs j with j % split_world == split_rank; the others' placements arrive
     // through the all-gather, and every rank commits all of them in row order.  split_world <= 1: everything is this rank's.
     int split_rank, split_world;
-    // commit (k_commit_scan / _apply / _finish)
+    // commit (k_commit_scan / _finish)
     CommitJob *cjob;               // [njobs] what the scan found out about a job
     int *chg;                      // [njobs][colcap] columns whose symbol for the row changes: y | old symbol << 24 | new symbol << 28
     int *evkey, *evdl;             // [njobs][EVCAP] structural events: 2y + 1 a column opens after y (+1), 2y column y is emptied (-1)
     int *insidx;                   // [njobs][Lmax] for a base that opens a column: its number among the row's new columns
     int *pair_cf, *pair_left;      // [njobs][njobs] (i, j > i): a change of job i lies in job j's interval; net columns job i opens left of it
-    BatchPlan *plan;               // which jobs of the batch commit (written by k_commit_apply's first work-group)
-    CommitEv *sev;                 // the batch's structural events, sorted (the same)
-    int *freed;                    // [EVCAP] slots of the columns the batch empties
     unsigned *ticket;              // arrivals at the end of k_commit_finish
 };
 #define NOT_MINE(JB, JOB) ((JB).split_world > 1 && (JOB) % (JB).split_world != (JB).split_rank)
@@ -3180,25 +3175,30 @@ __global__ __launch_bounds__(TB_W * 64) void k_trace_blk(DState st, JobBufs jb)
 // ---------------------------------------------------------------------------------------------
 // commit: Column_Updater (PW:1222-1243) for every existing column a realigned row touches, Column_Adder (PW:1245-1332) for
 // every column it opens, then W_Con (PW:706-763): drop the columns without a base and renumber -- for ALL the jobs of a batch
-// that may commit, spread over the chip in three launches (round 3: one work-group that walked the jobs one after the other,
-// 68 us per batch; a kernel boundary costs less than a grid barrier inside a launch, so the phases are launches):
+// that may commit, spread over the chip in two launches (round 3: one work-group that walked the jobs one after the other,
+// 68 us per batch; a kernel boundary costs less than a grid barrier inside a launch, so a phase that needs every work-group
+// of the one before is a launch -- and only such a phase):
 //   k_commit_scan    (job, share): WHAT a job's new placement changes, without touching the state: the columns whose symbol for
 //                    the row changes, the columns it opens (with their AlGapCount, PW:1305-1314 = coverage - rows ending there,
 //                    both without the row) and the columns it empties -- and which of that lies in the band interval of a LATER
 //                    job of the batch (the jobs of a batch are all gathered from the same state, in the same numbering);
-//   k_commit_apply   decides which jobs commit -- in row order; a job is exact iff no job committed before it changes anything
+//   k_commit_finish  decides which jobs commit -- in row order; a job is exact iff no job committed before it changes anything
 //                    inside its interval [lo, hi] (every column its DP read) and the clamps at the MSA's edges see the same
 //                    distances (PW:1496-1497, 1505); a job may go AHEAD of a stale one when their intervals are disjoint --,
-//                    applies the changes of all of them (their column sets are disjoint by that very rule), and copies the
-//                    stretches of the order that move out to a scratch array;
-//   k_commit_finish  moves them to their new ordinals, places the new columns, frees the emptied ones, and the last work-group
-//                    to arrive writes the header: width, row pointer, the next batch's size, the copy for the host.
+//                    applies the changes of all of them (their column sets are disjoint by that very rule), writes the order
+//                    under its new ordinals, new columns included, into the OTHER order buffer, and the last work-group to
+//                    arrive frees the emptied columns and writes the header: width, which buffer is current, row pointer, the
+//                    next batch's size, the copy for the host.
+// The changes and the renumbering were a launch each while the renumbering worked in place (source and target ranges of the
+// stretches that move overlap across work-groups).  Nothing else the renumbering reads comes from another work-group: the plan
+// and the sorted events every work-group works out for itself, and a new column's slot (aux[x]) is written and read by the same
+// thread.  The last arriver's ticket is the only synchronisation between the work-groups of the commit.
 // ---------------------------------------------------------------------------------------------
 #define COMMIT_NT 1024
 #define EVCAP 1024                  // structural events (columns opened / emptied) of one BATCH handled without a pass over the width
 #define MAXJ 128                    // jobs of a batch ("window" <= 128)
 #define CS_G 16                     // shares of a job in k_commit_scan
-#define CA_G 32                     // work-groups of k_commit_apply / k_commit_finish
+#define CA_G 32                     // work-groups of k_commit_finish
 
 // symbol of the realigned row in existing column y: base+? from a mark array inside [y0,y1], blank outside
 __device__ __forceinline__ int row_symbol(const uint8_t *mk, int y, int lo, int y0, int y1)
@@ -3220,7 +3220,7 @@ struct BatchPlan {
     int cjobs[MAXJ], slotbase[MAXJ];          // the committing jobs in row order; index of a job's first new column among the batch's
     signed char verdict[MAXJ];
 };
-struct CommitEv { int key[EVCAP], dl[EVCAP], skey[EVCAP], scum[EVCAP], seg_lo[EVCAP + 1], seg_sh[EVCAP + 1], seg_pre[EVCAP + 2]; int ns, cum, nev, pad; };
+struct CommitEv { int key[EVCAP], dl[EVCAP], skey[EVCAP], scum[EVCAP], del[EVCAP]; int cum, nev, ndel, pad; };   // (in LDS, one per work-group)
 
 __global__ __launch_bounds__(COMMIT_NT) void k_commit_scan(DState st, JobBufs jb, int njobs)
 {
@@ -3391,14 +3391,15 @@ __global__ __launch_bounds__(COMMIT_NT) void k_commit_scan(DState st, JobBufs jb
     }
 }
 
-// Which jobs of the batch commit (one thread; every work-group of k_commit_apply works it out for itself, from data no kernel
-// of the batch changes before k_commit_finish's last work-group).  Jobs in row order.  A stale job -- something a job committed
+// Which jobs of the batch commit (one thread; every work-group of k_commit_finish works it out for itself, from data nothing
+// in the batch changes before that kernel's last work-group, when all have arrived).  Jobs in row order.  A stale job -- something a job committed
 // before it changes lies in its interval -- is left for the next batch, and a later job may still commit AHEAD of it when the
 // two commute: their band intervals are disjoint (with a margin for the column a commit may open at its interval's edge, and
 // for the columns the commits before have opened or emptied inside the stale row's interval, which its NEXT gather will see
 // shifted by as many).  The DP depends on absolute positions only through the clamps at the MSA's edges, which disjoint
 // intervals rule out (commutation probe), so realigning j after i gives the state the reference reaches with j before i.
-__device__ void commit_decide(const DState &st, const JobBufs &jb, int njobs, BatchPlan *p, const JobMeta *metas, const CommitJob *cjobs, const int *pair_cf, const int *pair_left)
+// (skipped: MAXJ words of the caller's, in LDS -- as an array of this function's it was the kernel's only scratch memory)
+__device__ void commit_decide(const DState &st, const JobBufs &jb, int njobs, BatchPlan *p, const JobMeta *metas, const CommitJob *cjobs, const int *pair_cf, const int *pair_left, int *skipped)
 {
     const Hdr *h = st.hdr;
     p->idle = (h->status != 0 || h->need_grow) ? 1 : 0;
@@ -3411,7 +3412,6 @@ __device__ void commit_decide(const DState &st, const JobBufs &jb, int njobs, Ba
     if (p->idle) return;
     const int W = h->W, H = st.H, B = st.B;
     int net = 0, evabs = 0, nskip = 0;
-    int skipped[MAXJ];
     bool stopped = false;
     for (int j = 0; j < njobs && j < MAXJ; ++j) {
         const JobMeta *m = &metas[j];
@@ -3492,14 +3492,14 @@ __device__ void commit_decide(const DState &st, const JobBufs &jb, int njobs, Ba
 }
 
 // the events of the committing jobs, sorted by position (key 2y: column y is emptied, 2y+1: a column opens after y); an old
-// ordinal y moves by the sum of the events with key < 2y; only the stretches between events whose shifts do not cancel move
-__device__ void commit_sort_events(const JobBufs &jb, const BatchPlan *p, int W, CommitEv *ev)
+// ordinal y moves by the sum of the events with key < 2y (scum: the running sums); del: the emptied ordinals, in order
+__device__ void commit_sort_events(const JobBufs &jb, const BatchPlan *p, const CommitJob *cjobs, CommitEv *ev)
 {
     const int tid = threadIdx.x;
     int base = 0;
     for (int t = 0; t < p->ncommit; ++t) {
         const int j = p->cjobs[t];
-        const CommitJob *cj = &jb.cjob[j];
+        const CommitJob *cj = &cjobs[j];
         if (!cj->scanned) continue;
         const int n = min(cj->nev, EVCAP);
         for (int e = tid; e < n && base + e < EVCAP; e += COMMIT_NT) { ev->key[base + e] = jb.evkey[(size_t)j * EVCAP + e]; ev->dl[base + e] = jb.evdl[(size_t)j * EVCAP + e]; }
@@ -3515,53 +3515,76 @@ __device__ void commit_sort_events(const JobBufs &jb, const BatchPlan *p, int W,
     }
     __syncthreads();
     if (tid == 0) {
-        // running sums, and the segments of old ordinals that move: seg k = ordinals (after event k, up to event k+1]
-        int cum = 0, ns = 0, pre = 0;
+        int cum = 0, ndel = 0;
         for (int e = 0; e < nev; ++e) {
             cum += ev->scum[e];
             ev->scum[e] = cum;
-            const int lo_y = (ev->skey[e] >> 1) + 1;                               // first old ordinal after this event
-            const int hi_y = e + 1 < nev ? ((ev->skey[e + 1] & 1) ? (ev->skey[e + 1] >> 1) + 1 : (ev->skey[e + 1] >> 1)) : W;   // one past the last one before the next (a deleted column is not moved)
-            if (cum != 0 && hi_y > lo_y) { ev->seg_lo[ns] = lo_y; ev->seg_sh[ns] = cum; ev->seg_pre[ns] = pre; pre += hi_y - lo_y; ++ns; }
+            if (!(ev->skey[e] & 1)) ev->del[ndel++] = ev->skey[e] >> 1;
         }
-        ev->seg_pre[ns] = pre;
-        ev->ns = ns; ev->cum = cum; ev->nev = nev;
+        ev->cum = cum; ev->nev = nev; ev->ndel = ndel;
     }
     __syncthreads();
 }
 
-__global__ __launch_bounds__(COMMIT_NT) void k_commit_apply(DState st, JobBufs jb, int njobs)
+// The decision, the changes, the renumbering, then -- by the work-group that arrives last, when every other one has finished --
+// the header: the width, the k loop's row pointer (PW:1695 lives on the device), the size of the next batch.  A batch costs as
+// long as its longest fill, and rows that overlap the rows before them are almost always invalidated while the MSA is still
+// moving, so speculate just past the running mean of rows committed per batch -- and never let a speculative row make the batch
+// longer than its first row, the only one that is certain to commit.
+// NO work-group may leave before it has taken its ticket, whatever the batch holds: the ticket would stay one short, no header
+// would be written and the host's poll would run into its bound.
+__global__ __launch_bounds__(COMMIT_NT) void k_commit_finish(DState st, JobBufs jb, int njobs, const int *rowids, Hdr *host_copy, unsigned host_seq)
 {
     __shared__ BatchPlan sp;
     __shared__ CommitEv ev;
     __shared__ JobMeta s_meta[MAXJ];
     __shared__ CommitJob s_cj[MAXJ];
-    __shared__ int s_pcf[16 * 16], s_pl[16 * 16];
+    __shared__ int s_pcf[16 * 16], s_plf[16 * 16], s_skip[MAXJ];
+    __shared__ unsigned sh[COMMIT_NT / 64];
+    __shared__ int s_last, s_free, s_w;
+    __shared__ int s_pl[8], s_plo[64], s_phi[64], s_pL[64], s_pgap[64];
+    __shared__ unsigned long long s_ahead, s_okm, s_jm;
+    __shared__ unsigned s_ev;
+    __shared__ int s_bp[JR_BASE], s_sel[PLAN_MAX + 1], s_gp[PLAN_MAX + 1];
+    __shared__ __attribute__((aligned(16))) int s_hw[(sizeof(Hdr) + 3) / 4];
+    __shared__ int s_cw0[PLAN_CAND], s_cwL[PLAN_CAND], s_cL[PLAN_CAND], s_oldnext, s_rowend;
     const int tid = threadIdx.x;
+    Hdr *h = st.hdr;
+    const BatchPlan *p = &sp;
+    if (tid == 0) s_pl[0] = 0;
+    // the header as the batch found it (the last arriver writes it when every work-group has read it)
+    const int W = h->W, cur = h->cur, agree = h->agree;
+    const int nfree = h->nfree, nslots = h->nslots;
+    const int *order = cur ? st.order1 : st.order0;
+    int *norder = cur ? st.order0 : st.order1;
     {
         // what the decision reads, fetched by all threads at once (one thread walking it through dependent loads took as long
         // as the rest of the kernel)
         const int nj = min(njobs, MAXJ);
         for (int i = tid; i < nj * (int)(sizeof(JobMeta) / 4); i += COMMIT_NT) reinterpret_cast<int *>(s_meta)[i] = reinterpret_cast<const int *>(jb.meta)[i];
         for (int i = tid; i < nj * (int)(sizeof(CommitJob) / 4); i += COMMIT_NT) reinterpret_cast<int *>(s_cj)[i] = reinterpret_cast<const int *>(jb.cjob)[i];
-        if (njobs <= 16) for (int i = tid; i < njobs * njobs; i += COMMIT_NT) { s_pcf[i] = jb.pair_cf[i]; s_pl[i] = jb.pair_left[i]; }
+        if (njobs <= 16) for (int i = tid; i < njobs * njobs; i += COMMIT_NT) { s_pcf[i] = jb.pair_cf[i]; s_plf[i] = jb.pair_left[i]; }
         __syncthreads();
-        if (tid == 0) commit_decide(st, jb, njobs, &sp, s_meta, s_cj, njobs <= 16 ? s_pcf : jb.pair_cf, njobs <= 16 ? s_pl : jb.pair_left);
+        if (tid == 0) commit_decide(st, jb, njobs, &sp, s_meta, s_cj, njobs <= 16 ? s_pcf : jb.pair_cf, njobs <= 16 ? s_plf : jb.pair_left, s_skip);
     }
     __syncthreads();
-    if (blockIdx.x == 0)
-        for (int i = tid; i < (int)(sizeof(BatchPlan) / 4); i += COMMIT_NT) reinterpret_cast<int *>(jb.plan)[i] = reinterpret_cast<const int *>(&sp)[i];
-    if (sp.idle || sp.ncommit == 0) return;
-    const Hdr *h = st.hdr;
-    const int W = h->W;
-    const int *order = cur_order(st);
-    const int nfree = h->nfree, nslots = h->nslots;
     const int take = min(sp.nnew, nfree);
     const int gt = (int)blockIdx.x * COMMIT_NT + tid, GT = (int)gridDim.x * COMMIT_NT;
-    for (int t = 0; t < sp.ncommit; ++t) {
+    const bool work = !sp.idle && sp.ncommit > 0;
+    const bool fast = work && sp.restructure && !sp.big;                           // the order is renumbered from the list of events
+    // (the stretch of the order this thread will copy, asked for now: the loads are under way while the changes are made and
+    // the events sorted)
+    constexpr int CPY = 4;
+    const int s0 = max(0, min(sp.first, agree));
+    int cslot[CPY];
+#pragma unroll
+    for (int u = 0; u < CPY; ++u) { const int y = s0 + gt + u * GT; cslot[u] = (fast && y < W) ? order[y] : 0; }
+    // ---- the changes of the committing jobs, this work-group's share.  Every order[...] below reads the CURRENT buffer, which
+    // nobody writes in this launch.  (What the jobs are is read from the copies in LDS: no kernel writes it after the scan.)
+    for (int t = 0; work && t < sp.ncommit; ++t) {
         const int job = sp.cjobs[t];
-        const JobMeta *m = &jb.meta[job];
-        const CommitJob *cj = &jb.cjob[job];
+        const JobMeta *m = &s_meta[job];
+        const CommitJob *cj = &s_cj[job];
         if (!cj->scanned) continue;                                                // every base stays where it was
         const int k = m->k, L = m->L;
         const long long off = st.rowoff[k];
@@ -3585,7 +3608,7 @@ __global__ __launch_bounds__(COMMIT_NT) void k_commit_apply(DState st, JobBufs j
                 for (int b = 0; b < 6; ++b) nt.w[b] = ((b != bs) ? 1u : 0u) + ((b != 4) ? al : 0u);
                 nt.endcnt = (x == L - 1) ? 1u : 0u; nt.pad = 0;
                 st.tally[slot] = nt;
-                atomicAdd(&st.inscnt[y], 1);
+                if (sp.big) atomicAdd(&st.inscnt[y], 1);                           // (only the pass over the width reads it, and clears it)
             }
             aux[x] = slot;
             st.pos[off + x] = slot;
@@ -3610,77 +3633,36 @@ __global__ __launch_bounds__(COMMIT_NT) void k_commit_apply(DState st, JobBufs j
             *reinterpret_cast<uint4 *>(&tp->w[0]) = make_uint4(w[0], w[1], w[2], w[3]);
             *reinterpret_cast<uint2 *>(&tp->w[4]) = make_uint2(w[4], w[5]);
         }
-        // the row is one piece from now on: its inner segment ends are no ends any more (nbrk[k] is cleared by the finish)
+        // the row is one piece from now on: its inner segment ends are no ends any more (nbrk[k] is cleared with the header)
         const int nb = st.nbrk[k];
         const int *bx = st.brkx + st.brkoff[k];
         for (int i = gt; i < nb; i += GT) atomicSub(&st.tally[order[way[bx[i]]]].endcnt, 1u);
     }
-    if (!sp.restructure || sp.big) return;
-    // 3. W_Con (PW:706-763) + splice, first half: the stretches that move go out to a scratch array (source and target ranges
-    //    overlap); k_commit_finish brings them back under their new ordinals.  Every work-group sorts the events for itself.
-    commit_sort_events(jb, &sp, W, &ev);
-    if (blockIdx.x == 0) {
-        for (int i = tid; i < (int)(sizeof(CommitEv) / 4); i += COMMIT_NT) reinterpret_cast<int *>(jb.sev)[i] = reinterpret_cast<const int *>(&ev)[i];
-        // the slots of the emptied columns, read before anything moves
-        if (tid == 0) {
-            int pfree = 0;
-            for (int e = 0; e < ev.nev; ++e) if (!(ev.skey[e] & 1)) jb.freed[pfree++] = order[ev.skey[e] >> 1];
-        }
-    }
-    const int ns = ev.ns, total = ev.seg_pre[ns];
-    int *tmp = st.newidx;
-    auto seg_of = [&](int i) { int a = 0, b = ns - 1; while (a < b) { const int mid = (a + b + 1) >> 1; if (ev.seg_pre[mid] <= i) a = mid; else b = mid - 1; } return a; };
-    for (int i = gt; i < total; i += GT) { const int sgi = seg_of(i); tmp[i] = order[ev.seg_lo[sgi] + (i - ev.seg_pre[sgi])]; }
-}
-
-// Second half of the renumbering, then -- by the work-group that arrives last, when every other one has finished -- the header:
-// the width, the k loop's row pointer (PW:1695 lives on the device), the size of the next batch.  A batch costs as long as its
-// longest fill, and rows that overlap the rows before them are almost always invalidated while the MSA is still moving, so
-// speculate just past the running mean of rows committed per batch -- and never let a speculative row make the batch longer than
-// its first row, the only one that is certain to commit.
-__global__ __launch_bounds__(COMMIT_NT) void k_commit_finish(DState st, JobBufs jb, int njobs, const int *rowids, Hdr *host_copy, unsigned host_seq)
-{
-    __shared__ unsigned sh[COMMIT_NT / 64];
-    __shared__ int s_skey[EVCAP], s_scum[EVCAP], s_seg_lo[EVCAP + 1], s_seg_sh[EVCAP + 1], s_seg_pre[EVCAP + 2];
-    __shared__ int s_last, s_free, s_w;
-    __shared__ int s_pl[8], s_plo[64], s_phi[64], s_pL[64], s_pgap[64];
-    __shared__ unsigned long long s_ahead, s_okm, s_jm;
-    __shared__ unsigned s_ev;
-    __shared__ int s_bp[JR_BASE], s_sel[PLAN_MAX + 1], s_gp[PLAN_MAX + 1];
-    __shared__ __attribute__((aligned(16))) int s_hw[(sizeof(Hdr) + 3) / 4];
-    __shared__ int s_cw0[PLAN_CAND], s_cwL[PLAN_CAND], s_cL[PLAN_CAND], s_oldnext, s_rowend;
-    const int tid = threadIdx.x;
-    Hdr *h = st.hdr;
-    const BatchPlan *p = jb.plan;
-    if (tid == 0) s_pl[0] = 0;
-    const int W = h->W, cur = h->cur;
-    const int *order = cur ? st.order1 : st.order0;
-    int *norder = cur ? st.order0 : st.order1;
-    const int nfree = h->nfree, nslots = h->nslots;
-    const int take = min(p->nnew, nfree);
-    const int gt = (int)blockIdx.x * COMMIT_NT + tid, GT = (int)gridDim.x * COMMIT_NT;
-    int Wnew = W;
-    if (!p->idle && p->restructure && !p->big) {
-        const CommitEv *ev = jb.sev;
-        const int nev = ev->nev, ns = ev->ns;
-        for (int i = tid; i < nev; i += COMMIT_NT) { s_skey[i] = ev->skey[i]; s_scum[i] = ev->scum[i]; }
-        for (int i = tid; i <= ns; i += COMMIT_NT) { s_seg_lo[i] = ev->seg_lo[i]; s_seg_sh[i] = ev->seg_sh[i]; s_seg_pre[i] = ev->seg_pre[i]; }
-        __syncthreads();
-        const int total = s_seg_pre[ns];
-        const int *tmp = st.newidx;
-        int *ordw = const_cast<int *>(order);
-        auto seg_of = [&](int i) { int a = 0, b = ns - 1; while (a < b) { const int mid = (a + b + 1) >> 1; if (s_seg_pre[mid] <= i) a = mid; else b = mid - 1; } return a; };
-        for (int i = gt; i < total; i += GT) {
-            const int sgi = seg_of(i);
-            const int yn = s_seg_lo[sgi] + (i - s_seg_pre[sgi]) + s_seg_sh[sgi];
-            const int slot = tmp[i];
-            ordw[yn] = slot; st.rank[slot] = yn;
-        }
-        // the new columns: after old ordinal y, before any column opened there by a later base of the same row (PW:1245-1332)
+    if (fast) {
+        // ---- W_Con (PW:706-763) + splice, from the list of events: the order is written into the OTHER buffer, under the new
+        // ordinals.  In place, source and target ranges overlap across work-groups (it took a launch to copy the stretches that
+        // move out and another to bring them back); this way nothing that a work-group still reads is overwritten.  The other
+        // buffer holds the order of two renumberings ago and equals this one only on [0, agree): everything from
+        // min(first, agree) on is written, moved or not.  Every work-group sorts the events for itself.
+        commit_sort_events(jb, &sp, s_cj, &ev);
+        const int nev = ev.nev;
+        auto place = [&](int y, int slot) {
+            int a = 0, b = nev;                                                     // events with key < 2y
+            while (a < b) { const int mid = (a + b) >> 1; if (ev.skey[mid] < 2 * y) a = mid + 1; else b = mid; }
+            if (a < nev && ev.skey[a] == 2 * y) return;                             // emptied: its slot goes to the free list (below)
+            const int shy = a ? ev.scum[a - 1] : 0;
+            norder[y + shy] = slot;
+            if (shy) st.rank[slot] = y + shy;
+        };
+#pragma unroll
+        for (int u = 0; u < CPY; ++u) { const int y = s0 + gt + u * GT; if (y < W) place(y, cslot[u]); }
+        for (int y = s0 + gt + CPY * GT; y < W; y += GT) place(y, order[y]);        // (more than 131 072 columns to copy)
+        // the new columns: after old ordinal y, before any column opened there by a later base of the same row (PW:1245-1332);
+        // aux[x] is the slot this very thread gave the base above
         for (int t = 0; t < p->ncommit; ++t) {
             const int job = p->cjobs[t];
-            if (!jb.cjob[job].scanned || jb.meta[job].nnew == 0) continue;
-            const int L = jb.meta[job].L;
+            if (!s_cj[job].scanned || s_meta[job].nnew == 0) continue;
+            const int L = s_meta[job].L;
             const int *newcol = jb.newcol + (size_t)job * jb.Lmax;
             const int *aux = jb.aux + (size_t)job * jb.Lmax;
             for (int x = gt; x < L; x += GT) {
@@ -3690,24 +3672,40 @@ __global__ __launch_bounds__(COMMIT_NT) void k_commit_finish(DState st, JobBufs 
                     int tt = 0;
                     for (int xx = x - 1; xx >= 0 && newcol[xx] == c; --xx) ++tt;   // earlier bases opened there too
                     int a = 0, b = nev;                                             // events with key < 2y
-                    while (a < b) { const int mid = (a + b) >> 1; if (s_skey[mid] < 2 * y) a = mid + 1; else b = mid; }
-                    const int shy = a ? s_scum[a - 1] : 0;
-                    const int kept = (a < nev && s_skey[a] == 2 * y) ? 0 : 1;       // y itself emptied by this batch?
+                    while (a < b) { const int mid = (a + b) >> 1; if (ev.skey[mid] < 2 * y) a = mid + 1; else b = mid; }
+                    const int shy = a ? ev.scum[a - 1] : 0;
+                    const int kept = (a < nev && ev.skey[a] == 2 * y) ? 0 : 1;      // y itself emptied by this batch?
                     const int pnew = y + shy + kept + tt;
-                    ordw[pnew] = aux[x]; st.rank[aux[x]] = pnew;
-                    st.inscnt[y] = 0;
+                    norder[pnew] = aux[x]; st.rank[aux[x]] = pnew;
                 }
             }
         }
-        if (blockIdx.x == 0) for (int i = tid; i < p->ndel; i += COMMIT_NT) st.freelist[nfree - take + i] = jb.freed[i];
-        Wnew = W + ev->cum;
-    } else if (!p->idle && p->restructure && blockIdx.x == 0) {
-        // the same by a pass over the width (more than evcap events; one work-group): new ordinal of every surviving / new column.
+    }
+    // ---- the last work-group to get here goes on
+    // (every wave's stores are drained and the work-group's barrier passed before ONE lane releases them and takes a ticket;
+    // the last arriver's lane acquires before anybody of its work-group reads on)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        s_last = __hip_atomic_fetch_add(jb.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1 ? 1 : 0;
+        if (s_last) { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+    }
+    __syncthreads();
+    if (!s_last) return;
+    if (fast) {
+        // the slots of the emptied columns (the free list's top is what the work-groups took the new columns' slots from: it
+        // is written only now that all of them have), from this work-group's own sorted events
+        for (int i = tid; i < ev.ndel; i += COMMIT_NT) st.freelist[nfree - take + i] = order[ev.del[i]];
+        if (tid == 0) s_w = W + ev.cum;
+    } else if (work && sp.restructure) {
+        // the same by a pass over the width (more than evcap events; one work-group, and every work-group's tallies and
+        // counts of new columns are in): new ordinal of every surviving / new column.
         // Columns left of the first one that changes keep their ordinal, and the other order buffer already holds them as far
         // as the two agree, so the renumbering starts there
         if (tid == 0) s_free = 0;
         __syncthreads();
-        const int s0 = max(0, min(p->first, h->agree));
         unsigned carry = (unsigned)s0;
         for (int base = s0; base < W; base += COMMIT_NT) {
             const int y = base + tid;
@@ -3730,8 +3728,8 @@ __global__ __launch_bounds__(COMMIT_NT) void k_commit_finish(DState st, JobBufs 
         __syncthreads();
         for (int t = 0; t < p->ncommit; ++t) {
             const int job = p->cjobs[t];
-            if (!jb.cjob[job].scanned || jb.meta[job].nnew == 0) continue;
-            const int L = jb.meta[job].L;
+            if (!s_cj[job].scanned || s_meta[job].nnew == 0) continue;
+            const int L = s_meta[job].L;
             const int *newcol = jb.newcol + (size_t)job * jb.Lmax;
             const int *aux = jb.aux + (size_t)job * jb.Lmax;
             for (int x = tid; x < L; x += COMMIT_NT) {
@@ -3747,25 +3745,9 @@ __global__ __launch_bounds__(COMMIT_NT) void k_commit_finish(DState st, JobBufs 
                 }
             }
         }
-        if (tid == 0) s_w = (int)carry;
-        __syncthreads();
-        Wnew = s_w;
-        if (tid == 0) jb.sev->cum = Wnew - W;                                      // (for the work-group that writes the header)
+        if (tid == 0) s_w = (int)carry;                                            // (the new width, for the lane that writes the header)
     }
-    // ---- the last work-group to get here writes the header
-    // (every wave's stores are drained and the work-group's barrier passed before ONE lane releases them and takes a ticket;
-    // the last arriver's lane acquires before anybody of its work-group reads on)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        s_last = __hip_atomic_fetch_add(jb.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1 ? 1 : 0;
-        if (s_last) { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-    }
-    __syncthreads();
-    if (!s_last) return;
-    // The header is worked on in LDS: fetched by all threads at once, changed by lane 0 (a walk through a dozen cache lines of
+    // ---- the header.  It is worked on in LDS: fetched by all threads at once, changed by lane 0 (a walk through a dozen cache lines of
     // global memory, one dependent round trip each, was half of this kernel), written back and sent to the host by all.
     constexpr int HW = (int)(sizeof(Hdr) / 4);
     static_assert(HW <= COMMIT_NT, "one word of the header per thread");
@@ -3796,7 +3778,7 @@ __global__ __launch_bounds__(COMMIT_NT) void k_commit_finish(DState st, JobBufs 
             for (int j = 0; j < njobs && j < MAXJ; ++j) {
                 const int v = p->verdict[j];
                 if (v == V_NONE) break;
-                JobMeta *m = &jb.meta[j];
+                const JobMeta *m = &s_meta[j];
                 if (v == V_STOP_GROW) hh->need_grow = 1;
                 else if (v == V_STOP_ABORT) {
                     // k_fill_v3 gave this job up (time-out): it is realigned again, by k_fill_v2, as are the next batches
@@ -3819,7 +3801,7 @@ __global__ __launch_bounds__(COMMIT_NT) void k_commit_finish(DState st, JobBufs 
                     } else if (hh->warm_step > 0) hh->warm_cur = min(hh->warm_hi, hh->warm_cur + hh->warm_up);
                 } else if (v == V_STALE) hh->stop = 1;
                 else if (v == V_COMMIT) {
-                    const CommitJob *cj = &jb.cjob[j];
+                    const CommitJob *cj = &s_cj[j];
                     if (cj->scanned) {
                         version += 1;
                         if (cj->nchg > 0 || m->nnew > 0) hh->rows_changed += 1;
@@ -3838,12 +3820,12 @@ __global__ __launch_bounds__(COMMIT_NT) void k_commit_finish(DState st, JobBufs 
             hh->version = version;
             for (int i = 0; i < 4; ++i) hh->fail_reason[i] += (unsigned long long)p->reasons[i];
             if (p->restructure) {
-                const int cum = jb.sev->cum;
-                hh->W = W + cum;
+                hh->W = s_w;
                 hh->nslots = nslots + (p->nnew - take);
                 hh->nfree = nfree - take + p->ndel;
-                if (!p->big) hh->agree = max(0, min(hh->agree, min(p->first, W)));   // the other buffer was left alone
-                else { hh->cur = cur ^ 1; hh->agree = max(0, min(p->first, W)); }
+                // the renumbering wrote the other buffer, whichever way it went: that one is the order now, and the two agree
+                // on the columns left of the first one that changed
+                hh->cur = cur ^ 1; hh->agree = max(0, min(p->first, W));
             }
             // the rows of this batch that were picked ahead of rows outside it and have committed: what their intervals reach
             // beyond their bases, for the check of the rows they jumped (k_gather_a)
@@ -3851,7 +3833,7 @@ __global__ __launch_bounds__(COMMIT_NT) void k_commit_finish(DState st, JobBufs 
             if (s_bp[0]) {
                 for (int j = 0; j < njobs && j < PLAN_MAX; ++j) {
                     if (p->verdict[j] != V_COMMIT || s_bp[1 + PLAN_MAX + j] == 0x7fffffff) continue;
-                    const JobMeta *m = &jb.meta[j];
+                    const JobMeta *m = &s_meta[j];
                     if (m->off >= 64) continue;
                     const int *nc = jb.newcol + (size_t)j * jb.Lmax;
                     const int c0 = nc[0], cL = nc[m->L - 1];
@@ -3866,7 +3848,7 @@ __global__ __launch_bounds__(COMMIT_NT) void k_commit_finish(DState st, JobBufs 
             hh->events_total += (unsigned long long)p->nev;
             {
                 int nchg = 0;
-                for (int t = 0; t < p->ncommit; ++t) nchg += jb.cjob[p->cjobs[t]].scanned ? 1 : 0;
+                for (int t = 0; t < p->ncommit; ++t) nchg += s_cj[p->cjobs[t]].scanned ? 1 : 0;
                 if (nchg > 0) hh->evrate = 0.9f * hh->evrate + 0.1f * ((float)p->nev / (float)nchg);
             }
             const unsigned long long dm = hh->ahead | p->done_mask;
@@ -4512,15 +4494,12 @@ static int alloc_jobs(pwr_ctx *c, int njobs)
     if ((rc = dmalloc(c, &jb.insidx, (size_t)njobs * jb.Lmax))) return rc;
     if ((rc = dmalloc(c, &jb.pair_cf, (size_t)njobs * njobs))) return rc;
     if ((rc = dmalloc(c, &jb.pair_left, (size_t)njobs * njobs))) return rc;
-    if ((rc = dmalloc(c, &jb.plan, 1))) return rc;
-    if ((rc = dmalloc(c, &jb.sev, 1))) return rc;
-    if ((rc = dmalloc(c, &jb.freed, EVCAP))) return rc;
     if ((rc = dmalloc(c, &jb.ticket, 4))) return rc;
     if ((rc = dmalloc(c, &jb.chkdone, (size_t)njobs))) return rc;
     if (hipMemsetAsync(jb.chkdone, 0, sizeof(int) * (size_t)njobs, c->stream) != hipSuccess) return PWR_ERR_DEVICE;
     if (hipMemsetAsync(jb.cjob, 0, sizeof(CommitJob) * njobs, c->stream) != hipSuccess || hipMemsetAsync(jb.pair_cf, 0, sizeof(int) * (size_t)njobs * njobs, c->stream) != hipSuccess ||
-        hipMemsetAsync(jb.pair_left, 0, sizeof(int) * (size_t)njobs * njobs, c->stream) != hipSuccess || hipMemsetAsync(jb.plan, 0, sizeof(BatchPlan), c->stream) != hipSuccess ||
-        hipMemsetAsync(jb.sev, 0, sizeof(CommitEv), c->stream) != hipSuccess || hipMemsetAsync(jb.ticket, 0, 16, c->stream) != hipSuccess) return PWR_ERR_DEVICE;
+        hipMemsetAsync(jb.pair_left, 0, sizeof(int) * (size_t)njobs * njobs, c->stream) != hipSuccess ||
+        hipMemsetAsync(jb.ticket, 0, 16, c->stream) != hipSuccess) return PWR_ERR_DEVICE;
     if (hipMemset(jb.meta, 0, sizeof(JobMeta) * njobs) != hipSuccess) return PWR_ERR_DEVICE;
     c->job_allocs.assign(c->allocs.begin() + first, c->allocs.end());
     c->njobs = njobs;
@@ -4914,7 +4893,6 @@ static int enqueue_commit(pwr_ctx *c, Hdr *host_copy, unsigned host_seq)
 {
     const int n = c->window;
     hipLaunchKernelGGL(k_commit_scan, dim3(n, CS_G), dim3(COMMIT_NT), 0, c->stream, c->st, c->jb, n);
-    hipLaunchKernelGGL(k_commit_apply, dim3(CA_G), dim3(COMMIT_NT), 0, c->stream, c->st, c->jb, n);
     hipLaunchKernelGGL(k_commit_finish, dim3(CA_G), dim3(COMMIT_NT), 0, c->stream, c->st, c->jb, n, c->d_rowids, host_copy, host_seq);
     HIPC(hipGetLastError());
     return PWR_OK;
