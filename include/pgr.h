@@ -23,7 +23,9 @@
  * reference's SimDataAssessment.py (ProbabilityMatrix, MultiStepResolution: "SDA:" 359-391).  Last, for a labelling of the
  * rows, the consensus of every part and the differences between them on the device copy (pgr_cons_device.hip), and on those
  * the resolvability count of the reference's TransposonAssessment.py ("TA:"); and the way back, every row against every
- * part's consensus (pgr_assign_device.hip), which the reference does not have.
+ * part's consensus (pgr_assign_device.hip), which the reference does not have; nor has it the iteration of the two
+ * (pgr_settle_device.hip), the same comparison segment by segment with every row's best crossover between two parts
+ * (pgr_cross_device.hip) and the windows' labellings threaded into whole copies (pgr_thread, host).
  *
  * Floating point: only the ranking of the clique's candidates touches it (the hypergeometric tail, as in pmc.h: equal to
  * the reference's up to rounding, not bit for bit) and, in the k-means stage, the choice of the variables (both tails, against
@@ -379,6 +381,78 @@ void pgr_settlement_free(pgr_settlement *out);
 /* Duration of the last pgr_msa_settle, ms: [0] all, [1] checks, candidates, allocation and upload, [2] the planes kernel,
  * [3] the iterations in total, [4] the downloads.  (Kept per process, not per call.) */
 int  pgr_last_settle_timing(double *ms5);
+
+/* ---- rows that change copy: every row against every part per segment, and its best crossover (pgr_cross_device.hip) ---- */
+/* pgr_msa_assign compares a row with every part over all compared columns at once: a row that follows part A through the first
+ * segments and part B through the rest is a poor match of either.  THE REFERENCE HAS NO COUNTERPART: these semantics are this
+ * project's own.  h, parts, von, width, codes, ncolumns and columns as for pgr_msa_assign, base_code as there.  seg_end[nseg]
+ * cuts columns[] into consecutive segments: segment s holds the entries [seg_end[s - 1], seg_end[s]) of columns[], with
+ * seg_end[-1] = 0; seg_end ascends strictly and seg_end[nseg - 1] == ncolumns, so no segment is empty.
+ *   seg_mismatches[r][s][p], seg_compared[r][s] = what pgr_msa_assign defines as mismatches[r][p] and compared[r], over the
+ *                      columns of segment s alone.
+ *   compared, best, second, best_mismatches, second_mismatches = exactly what pgr_msa_assign returns for the same codes and
+ *                      columns: the one-copy explanation of the row.
+ *   seg_best[r][s]   = the part with the fewest mismatches in segment s, the lowest index among equals; -1 where
+ *                      seg_compared[r][s] == 0.
+ *   the crossover of row r, its two-copy explanation: a split k in 1 .. nseg - 1 is admissible when the row has at least
+ *                      min_side compared columns in the segments < k and at least min_side in the segments >= k.  For an
+ *                      admissible k and parts a != b, total(k, a, b) = the sum over s < k of seg_mismatches[r][s][a] + the sum
+ *                      over s >= k of seg_mismatches[r][s][b].  The crossover is the lexicographically smallest (total, k, a, b):
+ *                      cross_split[r] = k, cross_left[r] = a, cross_right[r] = b (part INDICES), cross_mismatches[r] = total,
+ *                      cross_left_compared[r] = the row's compared columns in the segments < k.  Where nseg < 2, parts < 2 or no
+ *                      split is admissible the three indices are -1 and the two counts 0.
+ * A split lies between two segments, never inside one (use finer segments), and a row has one crossover.  Everything is an
+ * integer, computed without atomics: no result depends on an order. */
+#define PGR_CX_MAX_SEGMENTS 1024 /* most segments of one call */
+
+typedef struct {
+    int rows, parts, ncolumns, nseg;
+    int *compared, *best, *second, *best_mismatches, *second_mismatches;   /* [rows] as pgr_assignment */
+    int *seg_compared;        /* [rows][nseg] */
+    int *seg_best;            /* [rows][nseg] part INDEX, or -1 */
+    int *cross_split;         /* [rows] 1 .. nseg-1, or -1 */
+    int *cross_left, *cross_right;   /* [rows] part INDEX, or -1 */
+    int *cross_mismatches;    /* [rows] */
+    int *cross_left_compared; /* [rows] */
+    int *seg_mismatches;      /* [rows][nseg][parts], or NULL unless asked for */
+} pgr_crossovers;
+
+/* Every segment is padded to whole words of 64 columns on the device (W = the sum over the segments of ceil(columns of the
+ * segment / 64)); the rows go through in ranges of at most PGR_AS_SCRATCH_BYTES / (32 * W + 4 * nseg * parts + 8 * nseg + 40)
+ * rows (one at least: the bit planes, the matrix and the per-row results), halved while the device refuses.  Errors as
+ * pgr_msa_assign (PWR_ERR_ARG: a null pointer, seg_end included; parts < 1; width < 1; a window outside the text; a code above 4;
+ * ncolumns < 1; columns that do not ascend strictly or lie outside the window; PWR_ERR_RANGE: parts > PGR_MAX_ROWS), and
+ * PWR_ERR_ARG for nseg < 1, a seg_end that does not ascend strictly from above 0 or does not end at ncolumns, and min_side < 1;
+ * PWR_ERR_RANGE for nseg > PGR_CX_MAX_SEGMENTS -- all refused before the device is touched.  want_matrix != 0 fills
+ * seg_mismatches.  *out is zeroed first and holds malloc'ed arrays (empty after a failure): release them with
+ * pgr_crossovers_free. */
+int  pgr_msa_crossovers(pgr_msa *h, int parts, int von, int width, const unsigned char *codes /* [parts][width], 0..4 */,
+                        int ncolumns, const int *columns, int nseg, const int *seg_end /* [nseg] */, int min_side, int want_matrix,
+                        pgr_crossovers *out);
+void pgr_crossovers_free(pgr_crossovers *out);
+/* Duration of the last pgr_msa_crossovers, ms: [0] all, [1] checks, padding, part planes, upload and allocation, [2] the planes
+ * kernel, [3] the segment distances, [4] the crossover and best kernels, [5] the downloads.  (Kept per process, not per call.) */
+int  pgr_last_crossover_timing(double *ms6);
+
+/* ---- host side, plain C (pgr_host.c): the windows' labellings threaded into whole copies ---- */
+/* The discrete counterpart of pgr_connect, integers only.  labels[nres][rows] as pgr_connect takes them (-1: the row is not in
+ * that labelling; flank labellings may stand in front and behind).  For neighbours i, i + 1: C_i[a][b] = the rows labelled
+ * a >= 0 in i and b >= 0 in i + 1.  (i, a) and (i + 1, b) are LINKED when C_i[a][b] > 0, b is the first largest of row a of C_i
+ * and a is the first largest of column b.  A thread is a maximal chain of links: every label that occurs in a labelling lies on
+ * exactly one thread, possibly alone.  Threads are numbered by (labelling, label) of their first element, ascending. */
+typedef struct {
+    int nres, rows, nthreads;
+    int *first, *last;        /* [nthreads] the labellings in which the thread begins and ends */
+    int *offset;              /* [nres + 1] offset[0] = 0, offset[i + 1] = offset[i] + k_i, k_i = (the largest label of labelling i) + 1 */
+    int *thread_of;           /* [offset[nres]] thread_of[offset[i] + label]; -1: the label does not occur in labelling i */
+    int *row_thread;          /* [rows] the thread common to all of the row's labels >= 0; -1: it has none, or they disagree */
+    int *row_conflict;        /* [rows] 1 exactly where they disagree */
+} pgr_threads;
+
+/* Errors as pgr_connect (PWR_ERR_ARG: a null pointer, nres < 2, rows <= 0, a label below -1, a labelling without a label >= 0).
+ * *out is zeroed first and holds malloc'ed arrays (empty after a failure): release them with pgr_threads_free. */
+int  pgr_thread(int nres, int rows, const int *labels, pgr_threads *out);
+void pgr_threads_free(pgr_threads *out);
 
 #ifdef __cplusplus
 }

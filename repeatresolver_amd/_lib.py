@@ -46,7 +46,8 @@ PGR_EXPORTS = ["pgr_refine", "pgr_free", "pgr_last_timing", "pgr_read_window", "
                "pgr_resolution_free", "pgr_last_resolve_timing", "pgr_connect", "pgr_connection_free", "pgr_msa_consensus",
                "pgr_consensus_free", "pgr_last_consensus_timing", "pgr_resolvability", "pgr_msa_assign", "pgr_assignment_free",
                "pgr_last_assign_timing", "pgr_msa_settle", "pgr_settlement_free", "pgr_last_settle_timing", "pgr_tail_probe",
-               "pgr_km_tail_probe"]
+               "pgr_km_tail_probe", "pgr_msa_crossovers", "pgr_crossovers_free", "pgr_last_crossover_timing", "pgr_thread",
+               "pgr_threads_free"]
 
 # every symbol include/pfl.h declares (the flank labellings)
 PFL_EXPORTS = ["pfl_create", "pfl_destroy", "pfl_neighbours", "pfl_distances", "pfl_cluster", "pfl_get_stats", "pfl_labels",
@@ -65,6 +66,8 @@ PGR_AS_TILE = 8               # parts per work-group of k_as_dist
 # (pgr_settle_device.hip) pgr_settlement.stop
 PGR_ST_CONVERGED, PGR_ST_MAX_ITER, PGR_ST_EMPTY, PGR_ST_NO_COLUMN = 0, 1, 2, 3
 PGR_ST_NAMES = ("CONVERGED", "MAX_ITER", "EMPTY", "NO_COLUMN")
+# (pgr_cross_device.hip)
+PGR_CX_MAX_SEGMENTS = 1024    # most segments of one pgr_msa_crossovers
 
 
 class PgrWindow(ctypes.Structure):
@@ -141,6 +144,19 @@ class PgrSettlement(ctypes.Structure):
                 ("ncolumns_at", ctypes.POINTER(ctypes.c_int)), ("ncolumns", ctypes.c_int), ("columns", ctypes.POINTER(ctypes.c_int)),
                 ("compared", ctypes.POINTER(ctypes.c_int)), ("best", ctypes.POINTER(ctypes.c_int)), ("second", ctypes.POINTER(ctypes.c_int)),
                 ("best_mismatches", ctypes.POINTER(ctypes.c_int)), ("second_mismatches", ctypes.POINTER(ctypes.c_int))]
+
+
+class PgrCrossovers(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_int), ("parts", ctypes.c_int), ("ncolumns", ctypes.c_int), ("nseg", ctypes.c_int)] + \
+        [(name, ctypes.POINTER(ctypes.c_int)) for name in
+         ("compared", "best", "second", "best_mismatches", "second_mismatches", "seg_compared", "seg_best", "cross_split", "cross_left",
+          "cross_right", "cross_mismatches", "cross_left_compared", "seg_mismatches")]
+
+
+class PgrThreads(ctypes.Structure):
+    _fields_ = [("nres", ctypes.c_int), ("rows", ctypes.c_int), ("nthreads", ctypes.c_int), ("first", ctypes.POINTER(ctypes.c_int)),
+                ("last", ctypes.POINTER(ctypes.c_int)), ("offset", ctypes.POINTER(ctypes.c_int)), ("thread_of", ctypes.POINTER(ctypes.c_int)),
+                ("row_thread", ctypes.POINTER(ctypes.c_int)), ("row_conflict", ctypes.POINTER(ctypes.c_int))]
 
 
 _lib = None
@@ -364,6 +380,16 @@ def load():
     lib.pgr_settlement_free.argtypes = [ctypes.POINTER(PgrSettlement)]
     lib.pgr_last_settle_timing.restype = ci
     lib.pgr_last_settle_timing.argtypes = [pd]
+    lib.pgr_msa_crossovers.restype = ci
+    lib.pgr_msa_crossovers.argtypes = [vp, ci, ci, ci, vp, ci, pi, ci, pi, ci, ci, ctypes.POINTER(PgrCrossovers)]
+    lib.pgr_crossovers_free.restype = None
+    lib.pgr_crossovers_free.argtypes = [ctypes.POINTER(PgrCrossovers)]
+    lib.pgr_last_crossover_timing.restype = ci
+    lib.pgr_last_crossover_timing.argtypes = [pd]
+    lib.pgr_thread.restype = ci
+    lib.pgr_thread.argtypes = [ci, ci, pi, ctypes.POINTER(PgrThreads)]
+    lib.pgr_threads_free.restype = None
+    lib.pgr_threads_free.argtypes = [ctypes.POINTER(PgrThreads)]
     for n in ("pmc_tail_probe", "pgr_tail_probe", "pgr_km_tail_probe"):   # test hooks (tail_probe.py)
         getattr(lib, n).restype = ci
         getattr(lib, n).argtypes = [ci, pi, pd, ci, pd]

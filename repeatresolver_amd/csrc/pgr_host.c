@@ -392,6 +392,112 @@ int pgr_connect(int nres, int rows, const int *labels, pgr_connection *out)
     return PWR_OK;
 }
 
+/* ---- the windows' labellings threaded into whole copies: the discrete counterpart of pgr_connect (no reference) ---- */
+
+void pgr_threads_free(pgr_threads *t)
+{
+    if (!t) return;
+    free(t->first); free(t->last); free(t->offset); free(t->thread_of); free(t->row_thread); free(t->row_conflict);
+    memset(t, 0, sizeof *t);
+}
+
+/* next[a] = the label of `r2` linked with label a of `r1`, -1: none; linked[b] = 1 where label b of r2 has such a partner */
+static int links(int rows, const int *r1, const int *r2, int k1, int k2, int *next, unsigned char *linked)
+{
+    int *C = calloc((size_t)k1 * k2, sizeof(int)), *col_best = malloc(sizeof(int) * (size_t)k2);
+    if (!C || !col_best) { free(C); free(col_best); return PWR_ERR_NOMEM; }
+    for (int t = 0; t < rows; t++)
+        if (r1[t] > -1 && r2[t] > -1) C[(size_t)r1[t] * k2 + r2[t]]++;
+    for (int b = 0; b < k2; b++) {                                                    /* the first largest of every column */
+        int best = 0;
+        for (int a = 1; a < k1; a++) if (C[(size_t)a * k2 + b] > C[(size_t)best * k2 + b]) best = a;
+        col_best[b] = best;
+        linked[b] = 0;
+    }
+    for (int a = 0; a < k1; a++) {
+        int best = 0;                                                                 /* the first largest of the row */
+        for (int b = 1; b < k2; b++) if (C[(size_t)a * k2 + b] > C[(size_t)a * k2 + best]) best = b;
+        next[a] = -1;
+        if (C[(size_t)a * k2 + best] > 0 && col_best[best] == a) { next[a] = best; linked[best] = 1; }
+    }
+    free(C); free(col_best);
+    return PWR_OK;
+}
+
+int pgr_thread(int nres, int rows, const int *labels, pgr_threads *out)
+{
+    if (!out) return PWR_ERR_ARG;
+    memset(out, 0, sizeof *out);
+    if (nres < 2 || rows <= 0 || !labels) return PWR_ERR_ARG;
+    int rc = PWR_OK, *next = NULL;
+    unsigned char *occurs = NULL, *linked = NULL;
+    out->offset = calloc((size_t)nres + 1, sizeof(int));
+    if (!out->offset) return PWR_ERR_NOMEM;
+    int *off = out->offset;
+    for (int i = 0; i < nres; i++) {                                                  /* as pgr_connect */
+        int max = -1;
+        for (int t = 0; t < rows; t++) {
+            const int l = labels[(size_t)i * rows + t];
+            if (l < -1) { rc = PWR_ERR_ARG; goto fail; }
+            if (l > max) max = l;
+        }
+        if (max < 0) { rc = PWR_ERR_ARG; goto fail; }
+        if (off[i] > 0x7fffffff - (max + 1)) { rc = PWR_ERR_RANGE; goto fail; }
+        off[i + 1] = off[i] + max + 1;
+    }
+    const size_t n = (size_t)off[nres];
+    out->nres = nres; out->rows = rows;
+    out->thread_of = malloc(sizeof(int) * n); out->first = malloc(sizeof(int) * n); out->last = malloc(sizeof(int) * n);
+    out->row_thread = malloc(sizeof(int) * (size_t)rows); out->row_conflict = malloc(sizeof(int) * (size_t)rows);
+    next = malloc(sizeof(int) * n); occurs = calloc(n, 1); linked = calloc(n, 1);
+    if (!out->thread_of || !out->first || !out->last || !out->row_thread || !out->row_conflict || !next || !occurs || !linked) {
+        rc = PWR_ERR_NOMEM;
+        goto fail;
+    }
+    for (int i = 0; i < nres; i++)
+        for (int t = 0; t < rows; t++)
+            if (labels[(size_t)i * rows + t] > -1) occurs[off[i] + labels[(size_t)i * rows + t]] = 1;
+    for (int i = 0; i + 1 < nres; i++) {
+        rc = links(rows, labels + (size_t)i * rows, labels + (size_t)(i + 1) * rows, off[i + 1] - off[i], off[i + 2] - off[i + 1],
+                   next + off[i], linked + off[i + 1]);
+        if (rc) goto fail;
+    }
+    for (int a = off[nres - 1]; a < off[nres]; a++) next[a] = -1;                      /* the last labelling links to nothing */
+    int threads = 0;
+    for (size_t e = 0; e < n; e++) out->thread_of[e] = -1;
+    for (int i = 0; i < nres; i++)
+        for (int a = 0; a < off[i + 1] - off[i]; a++) {
+            if (!occurs[off[i] + a] || linked[off[i] + a]) continue;                  /* no label, or not the first of its thread */
+            int j = i, l = a;
+            for (;;) {
+                out->thread_of[off[j] + l] = threads;
+                if (next[off[j] + l] < 0) break;
+                l = next[off[j] + l]; j++;
+            }
+            out->first[threads] = i; out->last[threads] = j;
+            threads++;
+        }
+    out->nthreads = threads;
+    for (int t = 0; t < rows; t++) {
+        int thread = -1, conflict = 0;
+        for (int i = 0; i < nres; i++) {
+            const int l = labels[(size_t)i * rows + t];
+            if (l < 0) continue;
+            const int x = out->thread_of[off[i] + l];
+            if (thread < 0) thread = x;
+            else if (thread != x) conflict = 1;
+        }
+        out->row_thread[t] = conflict ? -1 : thread;
+        out->row_conflict[t] = conflict;
+    }
+    free(next); free(occurs); free(linked);
+    return PWR_OK;
+fail:
+    free(next); free(occurs); free(linked);
+    pgr_threads_free(out);
+    return rc;
+}
+
 /* Resolvability (TransposonAssessment.py:97-119, "TA:") on the diff matrix of pgr_msa_consensus */
 int pgr_resolvability(int parts, const int *diff, int *unique11, int *min_diff, int *last_diff)
 {

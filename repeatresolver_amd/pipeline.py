@@ -167,10 +167,11 @@ def clustered(rows, von=None, bis=None, cov: int = 30, cutoff: float = 0.0, devi
     return sub, kmeans_subdivide(rows, refined, sub, von, bis, cov, device)
 
 
-def _resolved(rows, parts, coverage, cov, cutoff, device, copies, recruit=None, settle=None):
+def _resolved(rows, parts, coverage, cov, cutoff, device, copies, recruit=None, settle=None, thread=None):
     from .max_correlation import max_correlations
-    from .resolution import assign, connect, consensus, open_msa, resolve
+    from .resolution import assign, connect, consensus, crossovers, open_msa, resolve
     from .resolution import settle as settle_labels
+    from .resolution import thread as thread_labels
     from .window import window_boundaries
     assert not (recruit and settle)                                    # `assigned` or `settled`, one of them: each has its own return below
     sites = window_boundaries(rows, coverage, parts)
@@ -182,10 +183,19 @@ def _resolved(rows, parts, coverage, cov, cutoff, device, copies, recruit=None, 
         assignments = [None if c is None else assign(msa, c) for c in cons] if recruit else None
         settlements = [settle_labels(msa, w.kmeans_labels, w.von, w.bis, mc, w.cutoff, **settle) if w.kept_rows > 0 else None
                        for w in windows] if settle else None
+        settled_labels = [w.kmeans_labels.copy() if s is None else s.labels for w, s in zip(windows, settlements)] if settle else None
+        threads = whole = cross = None
+        if thread and len(windows) > 1:                                # the whole copies, while the MSA is still on the device
+            threads = thread_labels(settled_labels)
+            whole_labels = threads.labels()
+            if (whole_labels >= 0).any():
+                whole = consensus(msa, whole_labels, sites[0], sites[-1], mc, min(w.cutoff for w in windows))
+                cut = dict(segments=thread["segments"]) if thread["segments"] is not None else dict(segment_sites=sites[:-1])
+                cross = crossovers(msa, whole, min_side=thread["min_side"], **cut)
     con = connect([w.kmeans_labels for w in windows]) if len(windows) > 1 else None
     if settle:
-        settled_labels = [w.kmeans_labels.copy() if s is None else s.labels for w, s in zip(windows, settlements)]
-        return sites, windows, con, cons, settlements, connect(settled_labels) if len(windows) > 1 else None
+        settled = sites, windows, con, cons, settlements, connect(settled_labels) if len(windows) > 1 else None
+        return settled + (threads, whole, cross) if thread else settled
     if not recruit:
         return sites, windows, con, cons
     recruited = [w.kmeans_labels.copy() if a is None else a.labels(*recruit, keep=w.kmeans_labels) for w, a in zip(windows, assignments)]
@@ -238,3 +248,23 @@ def settled(rows, parts: int = 6, coverage: float = 0.90, cov: int = 30, cutoff:
     labellings are `assigned`'s recruited ones.  The thresholds and max_iter have no default."""
     return _resolved(rows, parts, coverage, cov, cutoff, device, True,
                      settle=dict(min_compared=min_compared, min_margin=min_margin, max_iter=max_iter, hold=hold))
+
+
+def threaded(rows, parts: int = 6, coverage: float = 0.90, cov: int = 30, cutoff: float = 0.0, device: int = 0, *, min_compared,
+             min_margin, max_iter, hold: bool = True, min_side, segments=None):
+    """settled, and the windows' settled labellings turned into whole copies, from the same device copy of the MSA.  Returns
+    settled's six values and
+      * the resolution.Threads of the settled labellings (resolution.thread): a label of one window and a label of the next are
+        linked where each is the other's first largest partner by shared rows, and a thread is a maximal chain of links,
+      * the resolution.Consensus of Threads.labels() -- every row whose labels all lie on one thread that spans all windows --
+        over [sites[0], sites[-1]], the selected columns being those over the smallest cutoff of the windows: the sequence of
+        every whole copy,
+      * the resolution.Crossovers of every row of the MSA against those whole copies (resolution.crossovers), the segments being
+        the windows (segment_sites = sites[:-1]) or, with `segments`, that many of equally many compared columns: the rows that
+        follow one copy up to a boundary and another behind it -- chimeric reads, misjoined rows, or two clusters joined
+        wrongly between windows -- are Crossovers.rows(min_gain).
+    A single window returns None for all three, no thread that spans all windows None for the last two.  min_side has no
+    default, like the other thresholds."""
+    return _resolved(rows, parts, coverage, cov, cutoff, device, True,
+                     settle=dict(min_compared=min_compared, min_margin=min_margin, max_iter=max_iter, hold=hold),
+                     thread=dict(min_side=min_side, segments=segments))

@@ -394,6 +394,152 @@ def last_settle_timing():
     return {"all_ms": t[0], "prepare_ms": t[1], "planes_ms": t[2], "iterations_ms": t[3], "download_ms": t[4]}
 
 
+@dataclass
+class Crossovers:
+    """pgr_crossovers (include/pgr.h): every row of the MSA against every part per segment of the compared columns, and per row
+    the best explanation by two different parts joined at a segment boundary.  The semantics are this project's own."""
+    von: int
+    bis: int
+    part_label: np.ndarray       # [parts] int32: the label that part index p stands for
+    columns: np.ndarray          # [ncolumns] int32 the compared columns, absolute, ascending
+    seg_end: np.ndarray          # [nseg] int32: segment s is columns[seg_end[s - 1]:seg_end[s]]
+    compared: np.ndarray         # [rows] the five fields of Assignment for the same codes and columns: the one-copy explanation
+    best: np.ndarray
+    second: np.ndarray
+    best_mismatches: np.ndarray
+    second_mismatches: np.ndarray
+    seg_compared: np.ndarray     # [rows, nseg] int32 compared columns of the segment in which the row has a symbol
+    seg_best: np.ndarray         # [rows, nseg] the part INDEX with the fewest mismatches in the segment; -1: nothing compared there
+    cross_split: np.ndarray      # [rows] k in 1 .. nseg - 1: part cross_left in the segments < k, cross_right from k on; -1: none
+    cross_left: np.ndarray       # [rows] part INDEX, or -1
+    cross_right: np.ndarray
+    cross_mismatches: np.ndarray     # [rows] the mismatches of that explanation
+    cross_left_compared: np.ndarray  # [rows] the row's compared columns in the segments < k
+    seg_mismatches: object       # [rows, nseg, parts] int32, or None unless asked for
+
+    @property
+    def segment_columns(self):
+        """one int32 array per segment: its compared columns"""
+        return np.split(self.columns, self.seg_end[:-1])
+
+    def rows(self, min_gain):
+        """the rows with a crossover that explains at least min_gain mismatches more than the best single part.  min_gain
+        depends on the read error rate, like Assignment.labels' thresholds: there is no default."""
+        return np.nonzero((self.cross_split >= 0) & (self.best_mismatches - self.cross_mismatches >= min_gain))[0]
+
+
+def _segment_ends(cols, segments, segment_sites):
+    if (segments is None) == (segment_sites is None):
+        raise ValueError("either segments or segment_sites")
+    n = len(cols)
+    if segments is not None:
+        if segments < 1 or segments > n:
+            raise ValueError("a segment would be empty")
+        return np.array([(s + 1) * n // segments for s in range(segments)], dtype=np.int32)
+    sites = np.asarray(segment_sites, dtype=np.int64)
+    if sites.ndim != 1 or len(sites) < 1 or (np.diff(sites) <= 0).any():
+        raise ValueError("segment_sites: ascending columns")
+    at = np.searchsorted(sites, cols, side="right") - 1            # the last site <= the column
+    count = np.bincount(at[at >= 0], minlength=len(sites))
+    if (at < 0).any() or (count == 0).any():
+        raise ValueError("a segment would be empty, or a compared column lies before the first site")
+    return np.cumsum(count).astype(np.int32)
+
+
+def crossover_sequences(msa: Msa, von: int, codes, columns, seg_end, *, min_side, part_label=None, matrix: bool = False) -> Crossovers:
+    """pgr_msa_crossovers (pgr_cross_device.hip): codes, columns and part_label as assign_sequences; seg_end: ascending ends of the
+    segments as indices into columns, the last one len(columns)."""
+    lib = _lib.load()
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    if codes.ndim != 2:
+        raise ValueError("codes: [parts, width]")
+    parts, width = codes.shape
+    cols = np.ascontiguousarray(columns, dtype=np.int32)
+    ends = np.ascontiguousarray(seg_end, dtype=np.int32)
+    if cols.ndim != 1 or ends.ndim != 1:
+        raise ValueError("columns and seg_end: lists")
+    part_label = np.arange(parts, dtype=np.int32) if part_label is None else np.array(part_label, dtype=np.int32)
+    if part_label.shape != (parts,):
+        raise ValueError("one label per part")
+    out = _lib.PgrCrossovers()
+    pi = ctypes.POINTER(ctypes.c_int)
+    _check(lib, lib.pgr_msa_crossovers(msa.handle, parts, von, width, codes.ctypes.data_as(ctypes.c_void_p), len(cols), cols.ctypes.data_as(pi),
+                                       len(ends), ends.ctypes.data_as(pi), min_side, 1 if matrix else 0, ctypes.byref(out)))
+    try:
+        T, S = out.rows, out.nseg
+        per_row = {name: _copy(getattr(out, name), (T,), np.int32)
+                   for name in ("compared", "best", "second", "best_mismatches", "second_mismatches", "cross_split", "cross_left",
+                                "cross_right", "cross_mismatches", "cross_left_compared")}
+        return Crossovers(von=von, bis=von + width - 1, part_label=part_label, columns=cols.copy(), seg_end=ends.copy(),
+                          seg_compared=_copy(out.seg_compared, (T, S), np.int32), seg_best=_copy(out.seg_best, (T, S), np.int32),
+                          seg_mismatches=_copy(out.seg_mismatches, (T, S, parts), np.int32) if matrix else None, **per_row)
+    finally:
+        lib.pgr_crossovers_free(ctypes.byref(out))
+
+
+def crossovers(msa: Msa, con: Consensus, *, segments=None, segment_sites=None, min_side, min_depth: int = 1, all_columns: bool = False,
+               matrix: bool = False) -> Crossovers:
+    """Every row of the MSA against the consensus of every part of `con` per segment, over the columns `assign` compares (same
+    min_depth and all_columns).  Either `segments`: that many segments of as equal a number of compared columns as possible, or
+    `segment_sites`: ascending absolute columns, a compared column c belonging to the segment of the last site <= c.  ValueError
+    when no column is left or a segment would be empty.  min_side has no default: it depends on the read error rate."""
+    cols = np.arange(con.von, con.bis + 1, dtype=np.int32) if all_columns else np.asarray(con.selected, dtype=np.int32)
+    cols = cols[(con.depth[:, cols - con.von] >= min_depth).all(axis=0)]
+    if len(cols) == 0:
+        raise ValueError("no column at which every part has the depth asked for")
+    return crossover_sequences(msa, con.von, con.consensus, cols, _segment_ends(cols, segments, segment_sites), min_side=min_side,
+                               part_label=con.part_label, matrix=matrix)
+
+
+def last_crossover_timing():
+    lib = _lib.load()
+    t = (ctypes.c_double * 6)()
+    lib.pgr_last_crossover_timing(t)
+    return {"all_ms": t[0], "prepare_ms": t[1], "planes_ms": t[2], "dist_ms": t[3], "cross_best_ms": t[4], "download_ms": t[5]}
+
+
+@dataclass
+class Threads:
+    """pgr_threads (include/pgr.h): the labellings of neighbouring windows threaded into whole copies.  Host only."""
+    nres: int
+    first: np.ndarray            # [threads] int32 the labelling in which the thread begins
+    last: np.ndarray             # [threads] and ends
+    offset: np.ndarray           # [nres + 1] into thread_of: labelling i's labels are thread_of[offset[i]:offset[i + 1]]
+    thread_of: np.ndarray        # the thread of every (labelling, label); -1: the label does not occur
+    row_thread: np.ndarray       # [rows] the thread common to all of the row's labels >= 0; -1: none, or they disagree
+    row_conflict: np.ndarray     # [rows] bool: they disagree
+
+    @property
+    def nthreads(self):
+        return len(self.first)
+
+    def labels(self, complete_only: bool = True):
+        """int32 [rows]: row_thread; with complete_only the rows of threads that do not span all labellings are -1"""
+        if not complete_only:
+            return self.row_thread.copy()
+        whole = (self.first == 0) & (self.last == self.nres - 1)
+        return np.where((self.row_thread >= 0) & whole[np.maximum(self.row_thread, 0)], self.row_thread, -1).astype(np.int32)
+
+
+def thread(label_vectors) -> Threads:
+    """label_vectors as `connect` takes them.  Labels of neighbouring labellings are linked where each is the other's first
+    largest partner by shared rows; a thread is a maximal chain of links (pgr_thread, include/pgr.h).  Host only."""
+    lib = _lib.load()
+    lab = np.ascontiguousarray(label_vectors, dtype=np.int32)
+    if lab.ndim != 2:
+        raise ValueError("label_vectors: equally long vectors")
+    out = _lib.PgrThreads()
+    _check(lib, lib.pgr_thread(lab.shape[0], lab.shape[1], lab.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ctypes.byref(out)))
+    try:
+        n, N, T = out.nthreads, out.nres, out.rows
+        offset = _copy(out.offset, (N + 1,), np.int32)
+        return Threads(nres=N, first=_copy(out.first, (n,), np.int32), last=_copy(out.last, (n,), np.int32), offset=offset,
+                       thread_of=_copy(out.thread_of, (int(offset[-1]),), np.int32), row_thread=_copy(out.row_thread, (T,), np.int32),
+                       row_conflict=_copy(out.row_conflict, (T,), np.int32).astype(bool))
+    finally:
+        lib.pgr_threads_free(ctypes.byref(out))
+
+
 def write_copies(path, consensus: Consensus, name: str):
     """One FASTA record per part, `>name_<von>_<bis>_copy<label> rows=<n>` and the sequence on one line.  The format is this
     project's own: the reference writes no consensus."""
