@@ -37,6 +37,42 @@
  * (single linkage); a component with fewer than min_size flanks gets -1, the others are numbered from 0 in the order of
  * their lowest flank index.  max_permille has no default: it depends on the reads' error rate (DESIGN 23 has the table).
  *
+ * ---- placement of a member against a backbone (pfl_place), integers only ----
+ * block: a multiple of 32 in 32 .. PFL_MAX_REACH; extent in block .. PFL_MAX_EXTENT; max_permille >= 0 (no default).  A
+ * BACKBONE is a plain sequence B, first base at the boundary.  Only its first nb = floor(min(|B|, extent) / block) blocks of
+ * `block` bases are used; a partial last block is dropped.  A MEMBER M is a flank's anchored sequence, its whole length.  It
+ * starts with the cursor s = 0, and for b = 0 .. nb - 1:
+ *     if |M| - s < block, the member stops;
+ *     P = block b of B (m = block), T = M[s : s + min(|M| - s, m + m / 4)], D as above (D(0,y) = y, D(x,0) = x, unit costs);
+ *     y* = the SMALLEST y in 0 .. |T| at which D(m, y) is minimal, d = D(m, y*);
+ *     if 1000 * d > max_permille * m, the member stops and casts no vote in this block;
+ *     otherwise the path is traced back from (m, y*) to (0, 0), at (x, y) taking
+ *         1. up        if x > 0 and D(x,y) = D(x-1,y) + 1      (the member lacks backbone base x - 1),
+ *         2. left      if y > 0 and D(x,y) = D(x,y-1) + 1      (member base y - 1 is inserted),
+ *         3. diagonal  otherwise,
+ *     and s += y*.
+ * With "up, then left, else diagonal" the gaps of equal-cost runs end up at the same end for every member, and only the +1
+ * halves of the vertical and horizontal deltas are needed.  Per member and used backbone position i the result is one byte
+ * ops[i]:
+ *     low nibble   0 .. 3: the member's base (a c g t) on a diagonal step; 4: an up step (a gap); 15: no vote;
+ *     high nibble  0, or 1 + the code of the FIRST member base of a run of left steps that directly follows position i.
+ * Left steps at x = 0, in front of a block's first base, vote for nothing: an insertion between two blocks, or in front of
+ * the backbone, is never seen.  This blind spot of one slot per block is part of the definition.  Also per member: the
+ * blocks it voted in, the bases it consumed (s at the end) and the sum of its d.
+ *
+ * ---- votes and call ----
+ * voters[i] = the members with a vote at i.  The symbol at i is the first largest of the counts of a, c, g, t, gap, in that
+ * order; a gap emits nothing.  After it, if 2 * (members with an insertion after i) > voters[i], the first largest inserted
+ * base (a, c, g, t in that order) is emitted too.  The consensus ends in front of the first i with voters[i] < min_depth
+ * (min_depth >= 1), and every emitted base carries voters[i] as its depth.
+ *
+ * ---- consensus of every cluster (pfl_consensus) ----
+ * For every label >= 0 among the flanks, ascending, the members are its flanks of at least `block` bases; a label of -1 is
+ * ignored.  Round 1's backbone is the longest member's anchored sequence (ties: the lowest flank index); it is itself a
+ * member and votes through its own alignment.  Round r + 1's backbone is round r's consensus, rounds >= 1.  A consensus
+ * shorter than `block` is the result, and that cluster's rounds stop.  A cluster without a member gets an empty consensus
+ * and backbone -1.  The consensus ends on a whole block of its backbone, so each round can lose up to block - 1 bases.
+ *
  * Error codes are those of pwr.h.
  */
 #ifndef PFL_H
@@ -52,6 +88,7 @@ extern "C" {
 
 #define PFL_MAX_REACH 512        /* 16 words of 32 pattern rows in a lane's registers */
 #define PFL_MAX_FLANKS 30000     /* flanks of one call (PGR_MAX_ROWS: there are no more rows) */
+#define PFL_MAX_EXTENT 8192      /* backbone bases a placement uses at most */
 
 typedef struct pfl_ctx pfl_ctx;
 
@@ -91,6 +128,52 @@ int pfl_labels(pfl_ctx *ctx, int npieces, const char *bases, const long long *of
                const unsigned char *strand, int max_permille, int reach, int min_len, int min_size, int *nrows, int *left,
                int *right);
 
+/* Every member against its backbone.  Flank k is given as in pfl_distances and belongs to backbone cluster[k] in 0 .. nb - 1,
+ * or to none (-1: it is not placed).  Backbone j is bb_bases[bb_off[j] .. bb_off[j + 1]), acgt in either case.  Of a member
+ * the min(len_k, extent + extent / 4) bases nearest to the boundary go to the device (no placement reaches further), once.
+ * ops[k * stride + i] is the byte above for i below the used bases of k's backbone and 15 for every other i < stride;
+ * blocks[k], used[k], dist[k] as above (0 for a flank that is not placed).  block, extent, n or nb out of range, or stride
+ * below the used bases of the longest backbone -> PWR_ERR_RANGE; null pointers, bad modes, pieces or clusters, descending
+ * offsets or max_permille < 0 -> PWR_ERR_ARG; a byte outside acgtACGT in a listed piece or in a backbone -> PWR_ERR_INPUT.
+ * All of these are found before the device is touched.  The traceback keeps 2 * (block / 32) * 4 * (block + block / 4) bytes
+ * per member in flight in a scratch buffer of the context; where that would pass the context's limit, or the device refuses
+ * it, the members go in ranges. */
+int pfl_place(pfl_ctx *ctx, int n, const char *bases, const long long *off, const int *piece, const int *mode, const int *cluster,
+              int nb, const char *bb_bases, const long long *bb_off, int block, int extent, int max_permille, unsigned char *ops,
+              long long stride, int *blocks, int *used, int *dist);
+
+/* The scratch a placement may take, in bytes (0 or less: the default, 1 GiB).  One tile of 64 members is always taken. */
+int pfl_set_scratch_limit(pfl_ctx *ctx, long long bytes);
+
+/* Cells (block * (block + block / 4) per member and block it voted in: the columns every lane steps) and the summed times of
+ * k_fl_place and k_fl_votes, ms, so far. */
+int pfl_get_place_stats(pfl_ctx *ctx, unsigned long long *cells, double *place_ms, double *votes_ms);
+
+typedef struct pfl_consensus_result {
+    int nclusters;               /* the labels >= 0 that occur */
+    int *label;                  /* [nclusters] ascending */
+    int *members;                /* [nclusters] flanks of the label with at least `block` bases */
+    int *backbone;               /* [nclusters] the flank index of round 1's backbone, or -1 */
+    long long *off;              /* [nclusters + 1]: cluster j's consensus is seq[off[j] .. off[j + 1]) */
+    char *seq;                   /* lower-case acgt, anchored: the first base lies at the repeat boundary */
+    int *depth;                  /* one per base of seq */
+} pfl_consensus_result;
+
+/* The consensus of every cluster, label[k] being flank k's label.  *out is zeroed first, filled on success (free it with
+ * pfl_consensus_free) and left zeroed on failure.  rounds < 1 and the ranges of pfl_place -> PWR_ERR_RANGE; min_depth < 1
+ * and the arguments of pfl_place -> PWR_ERR_ARG; PWR_ERR_INPUT as there.  Between rounds only the new backbones go up. */
+int pfl_consensus(pfl_ctx *ctx, int n, const char *bases, const long long *off, const int *piece, const int *mode, const int *label,
+                  int block, int extent, int max_permille, int min_depth, int rounds, pfl_consensus_result *out);
+void pfl_consensus_free(pfl_consensus_result *r);
+/* What pfl_consensus ends with, host only: the clusters' sequences seq[j][0 .. len[j]) and depths packed into *out (zeroed
+ * first; freed and left zeroed on failure).  A negative count or length, or a null where something is to be read -> PWR_ERR_ARG. */
+int pfl_consensus_pack(int nclusters, const int *label, const int *members, const int *backbone, const char *const *seq,
+                       const int *const *depth, const int *len, pfl_consensus_result *out);
+
+/* The call above on the votes of one backbone's npos positions, host only: sym[i] 0 .. 4 (4: gap), ins[i] 0 or 1 + base,
+ * voters[i].  seq and depth have room for 2 * npos entries; returns the number of bases emitted. */
+int pfl_call(int npos, const unsigned char *sym, const unsigned char *ins, const int *voters, int min_depth, char *seq, int *depth);
+
 /* ---- files, plain C ---- */
 /* ReadSeqInfo (prc_write_info: one line per read, its piece numbers each followed by a space): *piece_read (malloc'ed,
  * pfl_free) gets the read of every piece.  Numbers that do not count up from 0 -> PWR_ERR_INPUT. */
@@ -106,6 +189,17 @@ int pfl_write_labels(const char *path, int n, const int *labels);
  * Seq.fasta holds is an error. */
 int pfl_run_files(const char *seq_path, const char *info_path, const char *class_path, const char *strand_path, int max_permille,
                   int reach, int min_len, int min_size, const char *left_path, const char *right_path, int device, FILE *log);
+/* One record per cluster of r in template orientation, upper case, the sequence on one line: side "left" (the anchored
+ * consensus reversed, not complemented: it ends at the boundary) or "right" (as it is), headed
+ * ">left_<label> flanks=<members> bases=<n>". */
+int pfl_write_flank_fasta(const char *path, const char *side, const pfl_consensus_result *r);
+/* pfl_run_files, and with extent != 0 also pfl_consensus of every side's clusters (the flanks labelled by their rows'
+ * labels, max_permille as for the labels) to left_fasta and right_fasta through pfl_write_flank_fasta.  extent == 0 is
+ * pfl_run_files, and the four consensus parameters and the two paths are not looked at. */
+int pfl_run_files_consensus(const char *seq_path, const char *info_path, const char *class_path, const char *strand_path,
+                            int max_permille, int reach, int min_len, int min_size, const char *left_path, const char *right_path,
+                            int extent, int block, int min_depth, int rounds, const char *left_fasta, const char *right_fasta,
+                            int device, FILE *log);
 
 #ifdef __cplusplus
 }

@@ -51,9 +51,19 @@ PGR_EXPORTS = ["pgr_refine", "pgr_free", "pgr_last_timing", "pgr_read_window", "
 
 # every symbol include/pfl.h declares (the flank labellings)
 PFL_EXPORTS = ["pfl_create", "pfl_destroy", "pfl_neighbours", "pfl_distances", "pfl_cluster", "pfl_get_stats", "pfl_labels",
-               "pfl_read_info", "pfl_free", "pfl_write_labels", "pfl_run_files"]
+               "pfl_read_info", "pfl_free", "pfl_write_labels", "pfl_run_files", "pfl_place", "pfl_set_scratch_limit",
+               "pfl_get_place_stats", "pfl_consensus", "pfl_consensus_free", "pfl_consensus_pack", "pfl_call", "pfl_write_flank_fasta",
+               "pfl_run_files_consensus"]
 PFL_MAX_REACH = 512
 PFL_MAX_FLANKS = 30000
+PFL_MAX_EXTENT = 8192
+
+
+class PflConsensusResult(ctypes.Structure):
+    """pfl_consensus_result (include/pfl.h)"""
+    _fields_ = [("nclusters", ctypes.c_int), ("label", ctypes.POINTER(ctypes.c_int)), ("members", ctypes.POINTER(ctypes.c_int)),
+                ("backbone", ctypes.POINTER(ctypes.c_int)), ("off", ctypes.POINTER(ctypes.c_longlong)), ("seq", ctypes.c_void_p),
+                ("depth", ctypes.POINTER(ctypes.c_int))]
 
 # constants of include/pgr.h that tests and scripts cite (pgr_cons_device.hip)
 PGR_MAX_ROWS = 30000
@@ -416,5 +426,25 @@ def load():
     lib.pfl_write_labels.argtypes = [cp, ci, pi]
     lib.pfl_run_files.restype = ci
     lib.pfl_run_files.argtypes = [cp, cp, cp, cp, ci, ci, ci, ci, cp, cp, ci, vp]
+    cll = ctypes.c_longlong
+    pres = ctypes.POINTER(PflConsensusResult)
+    lib.pfl_place.restype = ci
+    lib.pfl_place.argtypes = [vp, ci, cp, pll, pi, pi, pi, ci, cp, pll, ci, ci, ci, pub, cll, pi, pi, pi]
+    lib.pfl_set_scratch_limit.restype = ci
+    lib.pfl_set_scratch_limit.argtypes = [vp, cll]
+    lib.pfl_get_place_stats.restype = ci
+    lib.pfl_get_place_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), pd, pd]
+    lib.pfl_consensus.restype = ci
+    lib.pfl_consensus.argtypes = [vp, ci, cp, pll, pi, pi, pi, ci, ci, ci, ci, ci, pres]
+    lib.pfl_consensus_free.restype = None
+    lib.pfl_consensus_free.argtypes = [pres]
+    lib.pfl_consensus_pack.restype = ci
+    lib.pfl_consensus_pack.argtypes = [ci, pi, pi, pi, ctypes.POINTER(cp), ctypes.POINTER(pi), pi, pres]
+    lib.pfl_call.restype = ci
+    lib.pfl_call.argtypes = [ci, pub, pub, pi, ci, cp, pi]
+    lib.pfl_write_flank_fasta.restype = ci
+    lib.pfl_write_flank_fasta.argtypes = [cp, cp, pres]
+    lib.pfl_run_files_consensus.restype = ci
+    lib.pfl_run_files_consensus.argtypes = [cp, cp, cp, cp, ci, ci, ci, ci, cp, cp, ci, ci, ci, ci, cp, cp, ci, vp]
     _lib = lib
     return lib

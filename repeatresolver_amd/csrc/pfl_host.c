@@ -109,6 +109,69 @@ int pfl_labels(pfl_ctx *ctx, int npieces, const char *bases, const long long *of
     return rc;
 }
 
+int pfl_call(int npos, const unsigned char *sym, const unsigned char *ins, const int *voters, int min_depth, char *seq, int *depth)
+{
+    int out = 0;
+    for (int i = 0; i < npos && voters[i] >= min_depth; i++) {
+        if (sym[i] < 4) { seq[out] = "acgt"[sym[i]]; depth[out++] = voters[i]; }   /* 4: the gap emits nothing */
+        if (ins[i]) { seq[out] = "acgt"[(ins[i] - 1) & 3]; depth[out++] = voters[i]; }
+    }
+    return out;
+}
+
+int pfl_consensus_pack(int nclusters, const int *label, const int *members, const int *backbone, const char *const *seq,
+                       const int *const *depth, const int *len, pfl_consensus_result *out)
+{
+    if (!out) return PWR_ERR_ARG;
+    memset(out, 0, sizeof *out);
+    if (nclusters < 0 || (nclusters && (!label || !members || !backbone || !seq || !depth || !len))) return PWR_ERR_ARG;
+    long long total = 0;
+    for (int j = 0; j < nclusters; j++) {
+        if (len[j] < 0 || (len[j] && (!seq[j] || !depth[j]))) return PWR_ERR_ARG;
+        total += len[j];
+    }
+    const size_t k = (size_t)nclusters;
+    out->label = malloc(sizeof(int) * (k + 1)); out->members = malloc(sizeof(int) * (k + 1)); out->backbone = malloc(sizeof(int) * (k + 1));
+    out->off = malloc(sizeof(long long) * (k + 1)); out->seq = malloc((size_t)total + 1); out->depth = malloc(sizeof(int) * ((size_t)total + 1));
+    if (!out->label || !out->members || !out->backbone || !out->off || !out->seq || !out->depth) { pfl_consensus_free(out); return PWR_ERR_NOMEM; }
+    out->nclusters = nclusters;
+    out->off[0] = 0;
+    for (int j = 0; j < nclusters; j++) {
+        out->label[j] = label[j]; out->members[j] = members[j]; out->backbone[j] = backbone[j];
+        if (len[j]) {
+            memcpy(out->seq + out->off[j], seq[j], (size_t)len[j]);
+            memcpy(out->depth + out->off[j], depth[j], sizeof(int) * (size_t)len[j]);
+        }
+        out->off[j + 1] = out->off[j] + len[j];
+    }
+    out->seq[total] = 0;
+    return PWR_OK;
+}
+
+void pfl_consensus_free(pfl_consensus_result *r)
+{
+    if (!r) return;
+    free(r->label); free(r->members); free(r->backbone); free(r->off); free(r->seq); free(r->depth);
+    memset(r, 0, sizeof *r);
+}
+
+int pfl_write_flank_fasta(const char *path, const char *side, const pfl_consensus_result *r)
+{
+    if (!path || !side || !r || (strcmp(side, "left") != 0 && strcmp(side, "right") != 0)) return PWR_ERR_ARG;
+    FILE *f = fopen(path, "w");
+    if (!f) return PWR_ERR_IO;
+    const int turn = side[0] == 'l';                                               /* template orientation: a left flank ends at the boundary */
+    for (int j = 0; j < r->nclusters; j++) {
+        const long long lo = r->off[j], n = r->off[j + 1] - lo;
+        fprintf(f, ">%s_%d flanks=%d bases=%lld\n", side, r->label[j], r->members[j], n);
+        for (long long x = 0; x < n; x++) fputc(r->seq[lo + (turn ? n - 1 - x : x)] - 32, f);
+        fputc('\n', f);
+    }
+    const int bad = ferror(f);
+    if (fclose(f) != 0 || bad) return PWR_ERR_IO;
+    return PWR_OK;
+}
+
 int pfl_read_info(const char *path, int *npieces, int **piece_read)
 {
     if (!path || !npieces || !piece_read) return PWR_ERR_ARG;
@@ -164,10 +227,40 @@ static int read_letters(const char *path, int n, int strands, char *out)
     return k == n ? PWR_OK : PWR_ERR_INPUT;
 }
 
+/* one side's consensus after the labels: the rows that have a flank there, labelled by their row's label, to path */
+static int side_consensus(pfl_ctx *ctx, int npieces, int nrows, const int *fpiece, const int *fmode, const int *label, const char *bases,
+                          const long long *off, int block, int extent, int max_permille, int min_depth, int rounds, const char *side,
+                          const char *path, FILE *log)
+{
+    int n = 0;
+    int *piece = malloc(sizeof(int) * ((size_t)npieces * 3 + 1));
+    if (!piece) return PWR_ERR_NOMEM;
+    int *mode = piece + npieces, *lab = piece + 2 * (size_t)npieces;
+    for (int t = 0; t < nrows; t++) if (fpiece[t] >= 0) { piece[n] = fpiece[t]; mode[n] = fmode[t]; lab[n] = label[t]; n++; }
+    pfl_consensus_result res;
+    int rc = pfl_consensus(ctx, n, bases, off, piece, mode, lab, block, extent, max_permille, min_depth, rounds, &res);
+    free(piece);
+    if (rc != PWR_OK) return rc;
+    rc = pfl_write_flank_fasta(path, side, &res);
+    if (rc == PWR_OK) fprintf(log, "%s: %d consensus sequences, %lld bases\n", side, res.nclusters, res.nclusters ? res.off[res.nclusters] : 0LL);
+    pfl_consensus_free(&res);
+    return rc;
+}
+
 int pfl_run_files(const char *seq_path, const char *info_path, const char *class_path, const char *strand_path, int max_permille,
                   int reach, int min_len, int min_size, const char *left_path, const char *right_path, int device, FILE *log)
 {
+    return pfl_run_files_consensus(seq_path, info_path, class_path, strand_path, max_permille, reach, min_len, min_size, left_path,
+                                   right_path, 0, 0, 0, 0, NULL, NULL, device, log);
+}
+
+int pfl_run_files_consensus(const char *seq_path, const char *info_path, const char *class_path, const char *strand_path,
+                            int max_permille, int reach, int min_len, int min_size, const char *left_path, const char *right_path,
+                            int extent, int block, int min_depth, int rounds, const char *left_fasta, const char *right_fasta,
+                            int device, FILE *log)
+{
     if (!seq_path || !info_path || !class_path || !left_path || !right_path || !log) return 1;
+    if (extent && (!left_fasta || !right_fasta)) return 1;
     int n = 0, ninfo = 0, nrows = 0, rc;
     char *bases = NULL, *cls = NULL, *strand = NULL;
     long long *off = NULL;
@@ -204,6 +297,17 @@ int pfl_run_files(const char *seq_path, const char *info_path, const char *class
                                       min_size, &nrows, left, right);
     if (rc == PWR_OK) rc = pfl_write_labels(left_path, nrows, left);
     if (rc == PWR_OK) rc = pfl_write_labels(right_path, nrows, right);
+    if (rc == PWR_OK && extent) {                                                  /* the sequence of every cluster, side by side */
+        int *nb = malloc(sizeof(int) * ((size_t)n * 5 + 1)), rows = 0;
+        const size_t np = (size_t)n;
+        if (!nb) rc = PWR_ERR_NOMEM;
+        if (rc == PWR_OK) rc = pfl_neighbours(n, piece_read, cls, (const unsigned char *)strand, &rows, nb, nb + np, nb + 2 * np, nb + 3 * np, nb + 4 * np);
+        if (rc == PWR_OK) rc = side_consensus(ctx, n, rows, nb + np, nb + 2 * np, left, bases, off, block, extent, max_permille, min_depth,
+                                              rounds, "left", left_fasta, log);
+        if (rc == PWR_OK) rc = side_consensus(ctx, n, rows, nb + 3 * np, nb + 4 * np, right, bases, off, block, extent, max_permille,
+                                              min_depth, rounds, "right", right_fasta, log);
+        free(nb);
+    }
     if (rc == PWR_OK) {
         int kl = 0, kr = 0, hl = 0, hr = 0;
         for (int t = 0; t < nrows; t++) {
@@ -216,7 +320,8 @@ int pfl_run_files(const char *seq_path, const char *info_path, const char *class
         fprintf(log, "rows %d\n", nrows);
         fprintf(log, "left: %d rows in %d clusters; right: %d rows in %d clusters\n", hl, kl, hr, kr);
         fprintf(log, "cells %llu, kernel %.3f ms\n", cells, ms);
-        fprintf(log, "Files written: %s %s\n", left_path, right_path);
+        if (extent) fprintf(log, "Files written: %s %s %s %s\n", left_path, right_path, left_fasta, right_fasta);
+        else fprintf(log, "Files written: %s %s\n", left_path, right_path);
     } else fprintf(log, "FlankClusterer: %s\n", pwr_strerror(rc));
     pfl_destroy(ctx);
     free(bases); free(off); free(piece_read); free(cls); free(strand); free(left); free(right);

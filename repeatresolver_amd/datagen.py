@@ -218,6 +218,17 @@ def simulate_dataset(cfg: SimConfig):
     Returns (template, full_reads, starts, copy_ids, cut_reads, cut_tpos): cut_reads[i] is the part of read i that the
     pipeline's ReadCutter keeps -- the stretch sampled from the repeat copy -- or None when the read lies in a flank.
     (Its own random stream: simulate()'s seeded workloads do not change.)"""
+    return _simulate_dataset(cfg)[0]
+
+
+def true_flanks(cfg: SimConfig):
+    """Per copy the (left, right) flank that simulate_dataset draws around it, as uint8 codes in template orientation: the
+    unique sequence a copy's reads run into.  From simulate_dataset's own loop, so the two cannot drift apart."""
+    return _simulate_dataset(cfg)[1]
+
+
+def _simulate_dataset(cfg: SimConfig):
+    """(simulate_dataset's value, true_flanks' value)"""
     rng = np.random.default_rng([cfg.seed, 0x5EED])
     seq = rng.integers(0, 4, size=cfg.repeat_len, dtype=np.uint8)
     if cfg.kind == "Tree":
@@ -230,10 +241,11 @@ def simulate_dataset(cfg: SimConfig):
         raise ValueError("kind must be Tree, Distributed or EquiDistant (DataSimulator.py:186)")
     prob = LENGTHS_HISTO / LENGTHS_HISTO.sum()
     fl = cfg.flank
-    full, starts, cids, cut_b, cut_t = [], [], [], [], []
+    full, starts, cids, cut_b, cut_t, flanks = [], [], [], [], [], []
     for c, (cb, ct) in enumerate(copies):
         left = rng.integers(0, 4, size=fl, dtype=np.uint8)                # DataSimulator.py:222-225
         right = rng.integers(0, 4, size=fl, dtype=np.uint8)
+        flanks.append((left, right))
         gb = np.concatenate((left, cb, right))
         gt = np.concatenate((np.full(fl, FLANK_MARK, np.int32), ct, np.full(fl, FLANK_MARK, np.int32)))
         glen = len(gb)
@@ -262,7 +274,7 @@ def simulate_dataset(cfg: SimConfig):
             else:
                 cut_b.append(None)
                 cut_t.append(None)
-    return seq, full, starts, cids, cut_b, cut_t
+    return (seq, full, starts, cids, cut_b, cut_t), flanks
 
 
 def write_dataset(prefix: str, cfg: SimConfig) -> dict:

@@ -7,6 +7,8 @@ import shutil
 import tempfile
 import time
 
+import numpy as np
+
 from . import datagen as dg
 from .initial_aligner import InitialAligner
 from .strands import seeded_mask, turn
@@ -186,9 +188,12 @@ def _resolved(rows, parts, coverage, cov, cutoff, device, copies, recruit=None, 
         settled_labels = [w.kmeans_labels.copy() if s is None else s.labels for w, s in zip(windows, settlements)] if settle else None
         threads = whole = cross = None
         if thread and len(windows) > 1:                                # the whole copies, while the MSA is still on the device
-            threads = thread_labels(settled_labels)
+            ends = thread.get("flanks")                                # `loci`: the flank labellings in front and behind
+            threads = thread_labels(settled_labels if ends is None else [ends[0], *settled_labels, ends[1]])
             whole_labels = threads.labels()
-            if (whole_labels >= 0).any():
+            if (whole_labels >= 0).any() and ends is not None:         # the copies over the full width, flank to flank
+                whole = consensus(msa, whole_labels, None, None, mc, min(w.cutoff for w in windows))
+            elif (whole_labels >= 0).any():
                 whole = consensus(msa, whole_labels, sites[0], sites[-1], mc, min(w.cutoff for w in windows))
                 cut = dict(segments=thread["segments"]) if thread["segments"] is not None else dict(segment_sites=sites[:-1])
                 cross = crossovers(msa, whole, min_side=thread["min_side"], **cut)
@@ -268,3 +273,25 @@ def threaded(rows, parts: int = 6, coverage: float = 0.90, cov: int = 30, cutoff
     return _resolved(rows, parts, coverage, cov, cutoff, device, True,
                      settle=dict(min_compared=min_compared, min_margin=min_margin, max_iter=max_iter, hold=hold),
                      thread=dict(min_side=min_side, segments=segments))
+
+
+def loci(rows, left, right, left_fc, right_fc, parts: int = 6, coverage: float = 0.90, cov: int = 30, cutoff: float = 0.0,
+         device: int = 0, *, min_compared, min_margin, max_iter, hold: bool = True, min_depth: int = 1):
+    """threaded with the two flank labellings (flank_labels' left and right, one label per row) in front of and behind the
+    settled ones, and every whole copy put back between its unique flanks.  Returns settled's six values and
+      * the resolution.Threads of [left, *settled labellings, right],
+      * the resolution.Consensus of Threads.labels() over the full width of the MSA (None where no thread spans from flank to
+        flank),
+      * the list of resolution.Locus that resolution.join_loci makes of them with left_fc and right_fc, the
+        flanks.FlankConsensus of the two sides (flanks.flank_sequences): left flank + copy + right flank per whole copy, the
+        copy over the columns of depth >= min_depth.
+    No crossovers are looked for here: `threaded` does that, between the windows alone."""
+    from .resolution import join_loci
+    left, right = np.asarray(left, dtype=np.int32), np.asarray(right, dtype=np.int32)
+    if left.shape != (len(rows),) or right.shape != (len(rows),):
+        raise ValueError("one left and one right label per row")
+    out = _resolved(rows, parts, coverage, cov, cutoff, device, True,
+                    settle=dict(min_compared=min_compared, min_margin=min_margin, max_iter=max_iter, hold=hold),
+                    thread=dict(min_side=None, segments=None, flanks=(left, right)))
+    threads, whole = out[6], out[7]
+    return out[:8] + ([] if whole is None else join_loci(threads, whole, left_fc, right_fc, min_depth),)

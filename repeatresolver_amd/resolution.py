@@ -548,6 +548,57 @@ def write_copies(path, consensus: Consensus, name: str):
             f.write(f">{name}_{consensus.von}_{consensus.bis}_copy{int(label)} rows={int(n)}\n".encode() + seq + b"\n")
 
 
+@dataclass
+class Locus:
+    """A whole copy between its unique flanks: what an assembly is patched with.  Host only."""
+    thread: int                  # the thread of Threads, and the label of its part in the whole Consensus
+    left_label: int              # the flank cluster in the first labelling
+    right_label: int             # and in the last
+    rows: int                    # rows of the part
+    left_len: int                # bases of the three pieces of `sequence`
+    copy_len: int
+    right_len: int
+    sequence: str                # left flank + copy + right flank, ACGT in template orientation
+
+
+def join_loci(threads: Threads, whole: Consensus, left_fc, right_fc, min_depth: int = 1):
+    """threads = thread([left, *labellings, right]) with the flank labellings at both ends, whole = the Consensus of
+    threads.labels(), left_fc / right_fc = the flanks.FlankConsensus of the two sides.  Every thread that spans all labellings
+    and has a part in `whole` gives a Locus: left_fc.oriented("left")[L] + copy + right_fc.oriented("right")[R], L and R being
+    the thread's labels in the first and the last labelling (a label the FlankConsensus does not hold adds nothing).  The copy
+    is the part's consensus over the columns with a base (code < 4) and depth >= min_depth: Consensus.sequences() would emit
+    an A for a column that no row of the part covers."""
+    if min_depth < 1:
+        raise ValueError("min_depth >= 1")
+    lefts, rights = left_fc.oriented("left"), right_fc.oriented("right")
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    ends = []
+    for i in (0, threads.nres - 1):
+        of = threads.thread_of[threads.offset[i]:threads.offset[i + 1]]
+        ends.append({int(t): label for label, t in enumerate(of) if t >= 0})
+    loci = []
+    for p, t in enumerate(whole.part_label):
+        t = int(t)
+        if not (0 <= t < threads.nthreads and threads.first[t] == 0 and threads.last[t] == threads.nres - 1):
+            continue
+        row, depth = whole.consensus[p], whole.depth[p]
+        copy = acgt[row[(row < 4) & (depth >= min_depth)]].tobytes().decode()
+        L, R = ends[0][t], ends[1][t]
+        left, right = lefts.get(L, ""), rights.get(R, "")
+        loci.append(Locus(thread=t, left_label=L, right_label=R, rows=int(whole.part_rows[p]), left_len=len(left), copy_len=len(copy),
+                          right_len=len(right), sequence=left + copy + right))
+    return loci
+
+
+def write_loci(path, loci, name: str):
+    """One FASTA record per Locus, `>name_locus<thread> left=<L>:<bases> copy=<bases> right=<R>:<bases> rows=<n>` and the sequence
+    on one line.  The format is this project's own."""
+    with open(path, "w") as f:
+        for l in loci:
+            f.write(f">{name}_locus{l.thread} left={l.left_label}:{l.left_len} copy={l.copy_len} right={l.right_label}:{l.right_len} "
+                    f"rows={l.rows}\n{l.sequence}\n")
+
+
 def unique_parts(diff):
     """Resolvability (TA:97-119) on a diff matrix: (unique[11], min_diff[parts], last_diff[parts]).  unique[t] = the parts whose
     smallest diff to any other part is > t; last_diff is what the reference itself returns -- the diff to the last other part
