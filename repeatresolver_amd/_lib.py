@@ -65,6 +65,45 @@ class PflConsensusResult(ctypes.Structure):
                 ("backbone", ctypes.POINTER(ctypes.c_int)), ("off", ctypes.POINTER(ctypes.c_longlong)), ("seq", ctypes.c_void_p),
                 ("depth", ctypes.POINTER(ctypes.c_int))]
 
+# every symbol include/pla.h declares (the locus anchorer)
+PLA_EXPORTS = ["pla_create", "pla_destroy", "pla_open_text", "pla_close_text", "pla_set_option", "pla_search", "pla_hits_free",
+               "pla_get_stats", "pla_read_contigs", "pla_contigs_free", "pla_read_loci", "pla_loci_free", "pla_place",
+               "pla_status_name", "pla_write_placements", "pla_write_patched", "pla_run_files"]
+PLA_MAX_REACH = 512
+PLA_MAX_HITS = 1 << 22
+PLA_MAX_PATTERNS = 65536
+PLA_RUN_CAP = 4
+PLA_STATUS_NAMES = ("NONE", "AMBIGUOUS", "LEFT_ONLY", "RIGHT_ONLY", "PLACED", "BRIDGE", "INCONSISTENT", "CONFLICT")
+PLA_NONE, PLA_AMBIGUOUS, PLA_LEFT_ONLY, PLA_RIGHT_ONLY, PLA_PLACED, PLA_BRIDGE, PLA_INCONSISTENT, PLA_CONFLICT = range(8)
+
+
+class PlaHits(ctypes.Structure):
+    """pla_hits (include/pla.h)"""
+    _fields_ = [("n", ctypes.c_int)] + [(name, ctypes.POINTER(ctypes.c_int)) for name in
+                                        ("pattern", "orientation", "contig", "boundary", "lo", "hi", "distance")]
+
+
+class PlaContigs(ctypes.Structure):
+    """pla_contigs"""
+    _fields_ = [("nc", ctypes.c_int), ("name", ctypes.POINTER(ctypes.c_char_p)), ("off", ctypes.POINTER(ctypes.c_longlong)),
+                ("bases", ctypes.c_void_p)]
+
+
+class PlaLoci(ctypes.Structure):
+    """pla_loci"""
+    _fields_ = [("n", ctypes.c_int), ("name", ctypes.POINTER(ctypes.c_char_p)), ("left_len", ctypes.POINTER(ctypes.c_int)),
+                ("copy_len", ctypes.POINTER(ctypes.c_int)), ("right_len", ctypes.POINTER(ctypes.c_int)),
+                ("off", ctypes.POINTER(ctypes.c_longlong)), ("seq", ctypes.c_void_p), ("aoff", ctypes.POINTER(ctypes.c_longlong)),
+                ("anchored", ctypes.c_void_p), ("side", ctypes.POINTER(ctypes.c_int))]
+
+
+class PlaPlacement(ctypes.Structure):
+    """pla_placement"""
+    _fields_ = [(name, ctypes.c_int) for name in
+                ("status", "left_hits", "right_hits", "left_contig", "left_orientation", "left_boundary", "left_distance",
+                 "right_contig", "right_orientation", "right_boundary", "right_distance", "lo", "hi", "has_span", "span")]
+
+
 # constants of include/pgr.h that tests and scripts cite (pgr_cons_device.hip)
 PGR_MAX_ROWS = 30000
 PGR_CS_TILE = 1024            # window columns per work-group of k_cs_counts
@@ -446,5 +485,40 @@ def load():
     lib.pfl_write_flank_fasta.argtypes = [cp, cp, pres]
     lib.pfl_run_files_consensus.restype = ci
     lib.pfl_run_files_consensus.argtypes = [cp, cp, cp, cp, ci, ci, ci, ci, cp, cp, ci, ci, ci, ci, cp, cp, ci, vp]
+    phits, pcon, ploci, ppl = ctypes.POINTER(PlaHits), ctypes.POINTER(PlaContigs), ctypes.POINTER(PlaLoci), ctypes.POINTER(PlaPlacement)
+    lib.pla_create.restype = ci
+    lib.pla_create.argtypes = [ctypes.POINTER(vp), ci]
+    lib.pla_destroy.restype = None
+    lib.pla_destroy.argtypes = [vp]
+    lib.pla_open_text.restype = ci
+    lib.pla_open_text.argtypes = [vp, ci, cp, pll]
+    lib.pla_close_text.restype = None
+    lib.pla_close_text.argtypes = [vp]
+    lib.pla_set_option.restype = ci
+    lib.pla_set_option.argtypes = [vp, cp, cll]
+    lib.pla_search.restype = ci
+    lib.pla_search.argtypes = [vp, ci, cp, pll, pi, ci, ci, ci, phits]
+    lib.pla_hits_free.restype = None
+    lib.pla_hits_free.argtypes = [phits]
+    lib.pla_get_stats.restype = ci
+    lib.pla_get_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), pd]
+    lib.pla_read_contigs.restype = ci
+    lib.pla_read_contigs.argtypes = [cp, pcon]
+    lib.pla_contigs_free.restype = None
+    lib.pla_contigs_free.argtypes = [pcon]
+    lib.pla_read_loci.restype = ci
+    lib.pla_read_loci.argtypes = [cp, ploci]
+    lib.pla_loci_free.restype = None
+    lib.pla_loci_free.argtypes = [ploci]
+    lib.pla_place.restype = ci
+    lib.pla_place.argtypes = [ci, pi, pi, phits, ci, ppl]
+    lib.pla_status_name.restype = cp
+    lib.pla_status_name.argtypes = [ci]
+    lib.pla_write_placements.restype = ci
+    lib.pla_write_placements.argtypes = [cp, ci, ctypes.POINTER(cp), ppl, pcon]
+    lib.pla_write_patched.restype = ci
+    lib.pla_write_patched.argtypes = [cp, pcon, ci, ppl, cp, pll]
+    lib.pla_run_files.restype = ci
+    lib.pla_run_files.argtypes = [cp, cp, ci, ci, ci, ci, cp, ci, vp]
     _lib = lib
     return lib

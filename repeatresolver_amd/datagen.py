@@ -227,8 +227,63 @@ def true_flanks(cfg: SimConfig):
     return _simulate_dataset(cfg)[1]
 
 
+def true_loci(cfg: SimConfig):
+    """Per copy (left flank, copy, right flank) as simulate_dataset lays them side by side, uint8 codes in template
+    orientation: what a perfect pipeline.loci would return.  From the same loop as true_flanks."""
+    flanks, copies = _simulate_dataset(cfg)[1:]
+    return [(left, cb, right) for (left, right), cb in zip(flanks, copies)]
+
+
+LAYOUTS = ("placed+", "placed-", "bridge", "left_only", "right_only", "none", "duplicated")
+
+
+def collapsed_assembly(cfg: SimConfig, layouts, spacer: int, seed: int):
+    """An assembly that collapsed the repeat: every copy's true flanks around the TEMPLATE instead of the copy, between
+    random spacers of `spacer` bases, one contig (or two) per copy.  layouts[c] says how copy c lies:
+      placed+      spacer + left + template + right + spacer
+      placed-      the reverse complement of that
+      bridge       the same cut in two inside the template: two contigs
+      left_only    the right flank is replaced by random bases;   right_only   the left flank is
+      none         both are
+      duplicated   placed+, and a second contig spacer + left + spacer: the left flank occurs twice
+    Returns (contigs, truth): contigs = [(name, bytes of acgt)], truth[c] = dict(layout, left=(contig, orientation, boundary)
+    or None, right=... or None), the boundary counting the contig's bases in front of it; a duplicated copy's left is the one
+    beside the template.  Its own random stream."""
+    from .strands import reverse_complement
+    loci = true_loci(cfg)
+    if len(layouts) != len(loci) or any(l not in LAYOUTS for l in layouts):
+        raise ValueError("one layout of LAYOUTS per copy")
+    rng = np.random.default_rng([seed, 0xA55E])
+    template = _simulate_dataset(cfg)[0][0]
+    text = lambda a: ASCII[a].tobytes().lower()
+    rand = lambda n: text(rng.integers(0, 4, size=n, dtype=np.uint8))
+    tb = text(template)
+    contigs, truth = [], []
+    for c, ((left, _cb, right), lay) in enumerate(zip(loci, layouts)):
+        lb = text(left) if lay not in ("right_only", "none") else rand(len(left))
+        rb = text(right) if lay not in ("left_only", "none") else rand(len(right))
+        head, tail = rand(spacer) + lb, rb + rand(spacer)
+        whole = head + tb + tail
+        at = len(contigs)
+        has_l, has_r = lay not in ("right_only", "none"), lay not in ("left_only", "none")
+        if lay == "placed-":
+            contigs.append((f"contig{at}", reverse_complement(whole)))
+            tl, tr = (at, 1, len(whole) - len(head)), (at, 1, len(whole) - len(head) - len(tb))
+        elif lay == "bridge":
+            h = len(tb) // 2
+            contigs += [(f"contig{at}", head + tb[:h]), (f"contig{at + 1}", tb[h:] + tail)]
+            tl, tr = (at, 0, len(head)), (at + 1, 0, len(tb) - h)
+        else:
+            contigs.append((f"contig{at}", whole))
+            tl, tr = (at, 0, len(head)), (at, 0, len(head) + len(tb))
+            if lay == "duplicated":
+                contigs.append((f"contig{at + 1}", rand(spacer) + lb + rand(spacer)))
+        truth.append(dict(layout=lay, left=tl if has_l else None, right=tr if has_r else None))
+    return contigs, truth
+
+
 def _simulate_dataset(cfg: SimConfig):
-    """(simulate_dataset's value, true_flanks' value)"""
+    """(simulate_dataset's value, true_flanks' value, the copies' bases)"""
     rng = np.random.default_rng([cfg.seed, 0x5EED])
     seq = rng.integers(0, 4, size=cfg.repeat_len, dtype=np.uint8)
     if cfg.kind == "Tree":
@@ -241,11 +296,12 @@ def _simulate_dataset(cfg: SimConfig):
         raise ValueError("kind must be Tree, Distributed or EquiDistant (DataSimulator.py:186)")
     prob = LENGTHS_HISTO / LENGTHS_HISTO.sum()
     fl = cfg.flank
-    full, starts, cids, cut_b, cut_t, flanks = [], [], [], [], [], []
+    full, starts, cids, cut_b, cut_t, flanks, bases = [], [], [], [], [], [], []
     for c, (cb, ct) in enumerate(copies):
         left = rng.integers(0, 4, size=fl, dtype=np.uint8)                # DataSimulator.py:222-225
         right = rng.integers(0, 4, size=fl, dtype=np.uint8)
         flanks.append((left, right))
+        bases.append(cb)
         gb = np.concatenate((left, cb, right))
         gt = np.concatenate((np.full(fl, FLANK_MARK, np.int32), ct, np.full(fl, FLANK_MARK, np.int32)))
         glen = len(gb)
@@ -274,7 +330,7 @@ def _simulate_dataset(cfg: SimConfig):
             else:
                 cut_b.append(None)
                 cut_t.append(None)
-    return (seq, full, starts, cids, cut_b, cut_t), flanks
+    return (seq, full, starts, cids, cut_b, cut_t), flanks, bases
 
 
 def write_dataset(prefix: str, cfg: SimConfig) -> dict:

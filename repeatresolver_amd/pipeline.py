@@ -295,3 +295,17 @@ def loci(rows, left, right, left_fc, right_fc, parts: int = 6, coverage: float =
                     thread=dict(min_side=None, segments=None, flanks=(left, right)))
     threads, whole = out[6], out[7]
     return out[:8] + ([] if whole is None else join_loci(threads, whole, left_fc, right_fc, min_depth),)
+
+
+def anchored(rows, left, right, left_fc, right_fc, contigs, parts: int = 6, coverage: float = 0.90, cov: int = 30, cutoff: float = 0.0,
+             device: int = 0, *, min_compared, min_margin, max_iter, hold: bool = True, min_depth: int = 1, anchor_permille, max_span,
+             reach: int = 256, min_len: int = 100):
+    """loci, and where its loci belong in an assembly (anchors.place_loci on the GPU: the `reach` bases of every locus's flanks
+    nearest to the repeat, searched in `contigs` in both orientations).  Returns loci's nine values and
+      * the anchors.Hits of the 2 n flank patterns (anchors.locus_patterns: 2 i is locus i's left flank, 2 i + 1 its right),
+      * the list of anchors.Placement, one per locus: anchors.patch(contigs, placements, copies) is the patched assembly.
+    anchor_permille (the search's max_permille) and max_span have no default."""
+    from .anchors import place_loci
+    out = loci(rows, left, right, left_fc, right_fc, parts, coverage, cov, cutoff, device, min_compared=min_compared,
+               min_margin=min_margin, max_iter=max_iter, hold=hold, min_depth=min_depth)
+    return out + place_loci(out[8], contigs, max_permille=anchor_permille, max_span=max_span, reach=reach, min_len=min_len, device=device)
